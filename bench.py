@@ -37,9 +37,15 @@ Multi-GPU (torchrun, one process per GPU):
       GpuBlsVerifier (integration/js), one verifySignatureSets([set], {batchable})
       per set, as gossip validation calls it (N = 1 only).
 
-Also reported: p50 latency of one non-batchable 128-set call (cfg1 shape), the
-roofline of the dominant kernel against the measured v_mad_u64_u32 peak, and the CPU
-baseline (the C++ restatement under oracle/cpu on the host cores, rank 0, N = 1).
+A plain run sets up, warms up, times the steps and prints the result line (metric,
+value, unit, ms_per_step, ...); --dump-outputs DIR also writes the verdicts the timed
+region's last passes returned (DIR/verdicts.npy).
+
+With --full also reported: p50 latency of one non-batchable 128-set call (cfg1 shape),
+the roofline of the dominant kernel against the measured v_mad_u64_u32 peak, the CPU
+baseline (the C++ restatement under oracle/cpu on the host cores, rank 0, N = 1), the
+latency curve, the cfg3 / cfg4 / cfg5 sub-records and the hardware-queue and
+torch-runtime child runs.
 """
 from __future__ import annotations
 
@@ -413,12 +419,14 @@ def timed_calls(ctxs, batches, steps: int):
     open while the others idle (with a fixed `steps` each, the contexts' pass times spread
     84-97 ms at 16 x 22 and the region ended on the slowest, tools/pass_gap_probe.py).
     Context i runs its own calls batches[i].  Returns (elapsed s, mean stage_ms, all
-    verdicts valid)."""
+    verdicts valid); timed_calls.outputs[i] holds the verdict arrays of context i's last
+    pass (None if it took no pass), for --dump-outputs."""
     n = len(ctxs)
     start = threading.Barrier(n + 1)
     stage_sum = np.zeros(8)
     ok = [True]
     shapes: dict[int, int] = {}
+    outputs: list = [None] * n
     lock = threading.Lock()
     left = [steps * n]
 
@@ -434,6 +442,7 @@ def timed_calls(ctxs, batches, steps: int):
         acc = np.zeros(8)
         good = True
         mine: dict[int, int] = {}
+        last = None
         while take():
             if isinstance(batches[i], list):
                 vs, st = ctxs[i].verify_many(batches[i])
@@ -441,11 +450,14 @@ def timed_calls(ctxs, batches, steps: int):
             else:
                 v, st = ctxs[i].verify_packed(batches[i])
                 good = good and bool((v == 1).all())
+                vs = [v]
+            last = vs
             acc += np.array(st.stage_ms[:])
             mine[st.pass_shape] = mine.get(st.pass_shape, 0) + 1
         with lock:
             stage_sum[:] += acc
             ok[0] = ok[0] and good
+            outputs[i] = last
             for k, c in mine.items():
                 shapes[k] = shapes.get(k, 0) + c
 
@@ -456,8 +468,30 @@ def timed_calls(ctxs, batches, steps: int):
     t0 = time.perf_counter()
     for t in th:
         t.join()
+    elapsed = time.perf_counter() - t0
     timed_calls.shapes = shapes  # pass_shape -> passes, for the roofline's work pricing
-    return time.perf_counter() - t0, stage_sum / max(1, steps * n), ok[0]
+    timed_calls.outputs = outputs
+    return elapsed, stage_sum / max(1, steps * n), ok[0]
+
+
+def dump_outputs(out_dir: str, ctxs, batches, rank: int = 0) -> dict:
+    """--dump-outputs: what the timed region's callers received from their last passes --
+    the verdict of every request (1 valid, 0 invalid), float32 [contexts, calls per pass,
+    requests per call], as DIR/verdicts.npy (rank r > 0 of a multi-GPU run:
+    verdicts.rank<r>.npy).  The inputs are the same from run to run (interop keys, sha256
+    messages, deterministic signatures), so two builds can be compared entry for entry.
+    A context that took no pass of the timed region (the passes go to whichever context
+    is idle) runs its calls once here, outside the region, so the array is complete."""
+    outs = list(getattr(timed_calls, "outputs", [None] * len(ctxs)))
+    for i, c in enumerate(ctxs):
+        if outs[i] is None:
+            outs[i] = c.verify_many(batches[i])[0] if isinstance(batches[i], list) else [c.verify_packed(batches[i])[0]]
+    arr = np.stack([np.stack([np.asarray(v, dtype=np.float32) for v in vs]) for vs in outs])
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    name = "verdicts.npy" if rank == 0 else f"verdicts.rank{rank}.npy"
+    np.save(d / name, arr)
+    return {"file": name, "shape": list(arr.shape), "dtype": str(arr.dtype)}
 
 
 def run_calls(ctxs, packed, calls_per_pass: int):
@@ -922,10 +956,18 @@ def main() -> None:
     ap.add_argument("--no-dedup", action="store_true", help="hash every set's root (BLS_DEBUG_NO_MSG_DEDUP)")
     ap.add_argument("--no-units", action="store_true",
                     help="one Miller loop per set even for shared roots (BLS_DEBUG_NO_UNITS)")
-    ap.add_argument("--no-sub-records", action="store_true", help="skip the cfg3 / cfg4 sub-records")
+    ap.add_argument("--no-sub-records", action="store_true", help="--full: skip the cfg3 / cfg4 sub-records")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure everything else the record holds: the 128-set call "
+                         "latency, the roofline (solo passes, the MAD peak), the CPU baseline, the latency curve, the "
+                         "cfg3 / cfg4 / cfg5 sub-records and the hardware-queue and torch-runtime child runs.  "
+                         "Without it a run sets up, warms up, times --steps steps and prints the result line")
     ap.add_argument("--probe-only", action="store_true",
-                    help="counter / trace runs: the warm-up and timed passes only (no latency, solo, peak or CPU "
-                         "legs), so a profile holds exactly those launches")
+                    help="the warm-up and timed passes only, so a counter / trace profile holds exactly those "
+                         "launches: what a run without --full does (kept for the profiling commands that pass it)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="--mode cfg2: after the timed steps write the verdicts the contexts' last timed passes "
+                         "returned to DIR/verdicts.npy (float32 [contexts, calls per pass, requests per call])")
     ap.add_argument("--table-keys", type=int, default=1 << 20, help="device pubkey table of the cfg3 / cfg4 records")
     ap.add_argument("--cfg4-sets", type=int, default=125_000,
                     help="sets of this GPU's cfg4 slice (1M sets over 8 GPUs by call)")
@@ -952,6 +994,10 @@ def main() -> None:
                     help="dry run of --mode cfg4 / cfg5 without a device: ranks on gloo, contexts from this CPU "
                          "stand-in (tests only)")
     args = ap.parse_args()
+    if not args.full:
+        args.probe_only = True
+    if args.dump_outputs and (args.mode != "cfg2" or args.stand_in):
+        raise SystemExit("--dump-outputs writes the cfg2 timed region's verdicts (--mode cfg2)")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # one rank per GPU, launched before this process touches the GPU
@@ -1173,6 +1219,8 @@ def _main_gpu(args, world, rank, local_rank, dist, device, share, barrier_sync, 
         barrier_sync()
         elapsed, stage_ms, ok = timed_calls(ctxs, [w[0] for w in works], args.steps)
         barrier_sync()
+        if args.dump_outputs:  # before the verdict check: a failing build's outputs show which requests differ
+            extra["outputs"] = dump_outputs(args.dump_outputs, ctxs, [w[0] for w in works], rank)
         if not ok:
             raise SystemExit("verification failed inside the timed region")
         local_sets = args.sets * K * args.steps * inflight

@@ -206,6 +206,43 @@ def test_work_pricing_follows_pass_shape():
     assert "k_pset" in note and small > bench.pset_products_per_set(1)
 
 
+class _FixedCtx:
+    """verify_many answering fixed verdicts (context c, call k: c + k for every request);
+    the `calls` of a pass are request counts.  The timed region's bookkeeping alone."""
+
+    def __init__(self, base: int):
+        self.base, self.passes = base, 0
+
+    def verify_many(self, calls):
+        self.passes += 1
+        return ([np.full(n, 1, dtype=np.int32) * (self.base + k) for k, n in enumerate(calls)],
+                SimpleNamespace(stage_ms=[0.0] * 8, pass_shape=0))
+
+
+def test_timed_steps_and_dumped_outputs(tmp_path):
+    """--steps sets the timed passes (steps x contexts, shared by the contexts), and
+    --dump-outputs writes what the contexts' last timed passes returned: float32
+    [contexts, calls per pass, requests per call]; a context that took no timed pass runs
+    its calls once outside the region, so the array is complete and the same every run."""
+    import bench
+
+    ctxs = [_FixedCtx(1), _FixedCtx(10)]
+    batches = [[5, 5, 5], [5, 5, 5]]
+    _, _, ok = bench.timed_calls(ctxs, batches, 3)
+    assert sum(c.passes for c in ctxs) == 3 * len(ctxs)
+    assert not ok  # verdicts other than 1 are failures of the timed region
+    want = np.array([[[c + k] * 5 for k in range(3)] for c in (1, 10)], dtype=np.float32)
+    info = bench.dump_outputs(str(tmp_path / "a"), ctxs, batches)
+    got = np.load(tmp_path / "a" / "verdicts.npy")
+    assert got.dtype == np.float32 and got.shape == (2, 3, 5) == tuple(info["shape"])
+    assert (got == want).all()
+    before = ctxs[1].passes
+    bench.timed_calls.outputs[1] = None  # as if context 0 had taken every pass
+    bench.dump_outputs(str(tmp_path / "b"), ctxs, batches)
+    assert ctxs[1].passes == before + 1
+    assert (np.load(tmp_path / "b" / "verdicts.npy") == want).all()
+
+
 def test_bench_gpus2_launches_two_ranks():
     """`bench.py --gpus 2` with no launcher starts two rank processes itself (RANK /
     WORLD_SIZE / LOCAL_RANK, rendezvous on 127.0.0.1) and rank 0 reports n_gpus 2 -- here

@@ -10,7 +10,7 @@ if [ -n "$TESTS" ]; then
   timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --timeout 400 --timeout-method thread > $O/pytest.log 2>&1 || { echo "pytest failed"; tail -30 $O/pytest.log; exit 1; }
   tail -1 $O/pytest.log
 fi
-B="python -u bench.py --steps ${STEPS:-8} --warmup 1 --no-cpu-baseline --no-sub-records --latency-runs 10"
+B="python -u bench.py --full --steps ${STEPS:-8} --warmup 1 --no-cpu-baseline --no-sub-records --latency-runs 10"
 # CFGS: "16x8 12x12" (contexts x calls per pass); ENVS: env assignments applied to every line,
 # each A/B label separated by ";" as "label:VAR=v,VAR2=w" ("base:" = no extra variables)
 for ab in $(echo "${ENVS:-base:}" | tr ';' ' '); do
@@ -23,7 +23,7 @@ for ab in $(echo "${ENVS:-base:}" | tr ';' ' '); do
  done
 done
 if [ -n "$SUB" ]; then
-  timeout -k 10 400 python -u bench.py --steps 2 --warmup 1 --no-cpu-baseline --latency-runs 3 --inflight 16 > $O/sub.json 2> $O/sub.err || { echo "sub failed"; tail $O/sub.err; exit 1; }
+  timeout -k 10 400 python -u bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --latency-runs 3 --inflight 16 > $O/sub.json 2> $O/sub.err || { echo "sub failed"; tail $O/sub.err; exit 1; }
   python3 -c "import json;d=json.load(open('$O/sub.json'));print(d['value'], {k:(d[k].get('sets_per_s'),d[k].get('p50_ms')) for k in ('cfg3','cfg4_slice','cfg4_slice_batchable')})"
 fi
 if [ -n "$PMC" ]; then

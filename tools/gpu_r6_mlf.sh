@@ -13,7 +13,7 @@ if [ -n "$TESTS" ]; then
   timeout -k 10 600 python -u -m pytest tests -m gpu -x -q --timeout 400 --timeout-method thread ${TESTK:+-k "$TESTK"} > $O/pytest.log 2>&1 || { echo "pytest failed"; tail -40 $O/pytest.log; exit 1; }
   tail -1 $O/pytest.log
 fi
-B="python -u bench.py --steps ${STEPS:-8} --warmup 2 --no-cpu-baseline --no-sub-records --latency-runs 10"
+B="python -u bench.py --full --steps ${STEPS:-8} --warmup 2 --no-cpu-baseline --no-sub-records --latency-runs 10"
 for ab in $(echo "${ENVS:-base:}" | tr ';' ' '); do
   label=${ab%%:*}; vars=$(echo "${ab#*:}" | tr ',' ' ')
   for cfg in ${CFGS}; do
