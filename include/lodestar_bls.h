@@ -288,6 +288,26 @@ int bls_gpu_mad_peak(bls_gpu_ctx* ctx, double* mads_per_s, double* ms);
  * elements (exercises to/from Montgomery and the device Montgomery product). */
 int bls_gpu_fp_mul_test(bls_gpu_ctx* ctx, const uint8_t* a48, const uint8_t* b48, uint32_t n, uint8_t* out48);
 
+/* Device field-op self-test: one lane per record runs ONE field primitive on raw
+ * little-endian 32-bit words (Fp = 12 limbs, lazy28 = 14 signed digits) and writes its
+ * raw result; nothing converts to or from Montgomery form or reduces around it, so
+ * non-canonical operands reach the primitive untouched.  `in` holds n records of
+ * in_words words, `out` receives n records of out_words (bls_gpu_field_op_shape).
+ * op: a base id (lodestar_amd/csrc/kernels/field_ops.hpp FOP_*, tests/_fieldvec.py),
+ * ORed with BLS_FIELD_OP_D28 for the kernels built over the 28-bit-digit product the
+ * verify path uses; without it the 32-bit column product.  -2: unknown op. */
+#define BLS_FIELD_OP_D28 0x100u
+int bls_gpu_field_op_test(bls_gpu_ctx* ctx, uint32_t op, const uint32_t* in, uint32_t n, uint32_t* out);
+int bls_gpu_field_op_shape(uint32_t op, uint32_t* in_words, uint32_t* out_words);
+
+/* Interpreter test: the cooperative program `name` of the loaded table run once on each
+ * of n_frames frames of n_slots raw Fp values (12 little-endian words each, Montgomery
+ * form, any representative below 3p); frames_out receives the raw frames after the run
+ * (lazy values, not canonicalised) and flags_out one zero-check flag word per frame.
+ * n_slots must equal the program's frame size in the table (-2 otherwise). */
+int bls_gpu_coop_run_test(bls_gpu_ctx* ctx, const char* name, const uint32_t* frames_in, uint32_t n_frames,
+                          uint32_t n_slots, uint32_t* frames_out, uint32_t* flags_out);
+
 /* Probe: `lanes` lanes each run `iters` dependent Montgomery products. */
 int bls_gpu_fpm_bench(bls_gpu_ctx* ctx, uint32_t lanes, uint32_t iters, double* ns_per_fpm, double* fpm_per_s);
 

@@ -74,6 +74,7 @@ struct bls_gpu_ctx {
   CoopEnv coop;
   void* coop_dev;
   std::vector<std::pair<std::string, CoopProg>>* coop_progs;
+  std::vector<uint32_t>* coop_frames;  // frame size (slots) of coop_progs[k], from the table
   // one call at a time per context: every entry point that touches the stream,
   // workspace or table holds this (callers may share a context across threads)
   std::mutex* mu;
@@ -257,11 +258,13 @@ static int load_coop_tables(bls_gpu_ctx* ctx) {
               {"ml1_1", &ctx->coop.ml1_1},
               {"ml1_2", &ctx->coop.ml1_2}};
   ctx->coop_progs = new std::vector<std::pair<std::string, CoopProg>>();
+  ctx->coop_frames = new std::vector<uint32_t>();
   for (uint32_t k = 0; k < h.n_progs; ++k) {
     CoopProgEntry e;
     memcpy(&e, buf.data() + progs_off + k * sizeof(e), sizeof(e));
     e.name[31] = 0;
     ctx->coop_progs->push_back({std::string(e.name), CoopProg{e.first, e.n_steps}});
+    ctx->coop_frames->push_back(e.frame);
   }
   // packed programs (tools/gen_pset.py S = 2, 3): pset{S}_{prep, dbl_all, add_x, ...}
   std::vector<std::pair<std::string, CoopProg*>> want_packed;
@@ -570,6 +573,7 @@ void bls_gpu_close(bls_gpu_ctx* ctx) {
     if (ctx->ev[i]) (void)hipEventDestroy(ctx->ev[i]);
   if (ctx->coop_dev) (void)hipFree(ctx->coop_dev);
   delete ctx->coop_progs;
+  delete ctx->coop_frames;
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx->mu;
   delete ctx;
@@ -2295,6 +2299,33 @@ extern "C" int bls_gpu_fp_mul_test(bls_gpu_ctx* ctx, const uint8_t* a48, const u
   return 0;
 }
 
+extern "C" int bls_gpu_field_op_shape(uint32_t op, uint32_t* in_words, uint32_t* out_words) {
+  return field_op_shape(op, in_words, out_words);
+}
+
+// One field primitive per lane on raw words (kernels/field_ops.hpp): n records of the
+// op's in_words in, n of its out_words out.
+extern "C" int bls_gpu_field_op_test(bls_gpu_ctx* ctx, uint32_t op, const uint32_t* in, uint32_t n, uint32_t* out) {
+  CTX_LOCK(ctx);
+  HIPC(ctx, hipSetDevice(ctx->device));
+  uint32_t iw = 0, ow = 0;
+  if (field_op_shape(op, &iw, &ow) != 0) {
+    snprintf(ctx->err, sizeof(ctx->err), "unknown field op 0x%x", op);
+    return -2;
+  }
+  if (n == 0) return 0;
+  const size_t in_sz = 4ull * iw * n, out_sz = 4ull * ow * n, in_al = (in_sz + 255) & ~(size_t)255;
+  if (ensure_dev(ctx, in_al + out_sz)) return -1;
+  uint32_t *din = (uint32_t*)ctx->dev_ws, *dout = (uint32_t*)(ctx->dev_ws + in_al);
+  hipStream_t s = ctx->stream;
+  HIPC(ctx, hipMemcpyAsync(din, in, in_sz, hipMemcpyHostToDevice, s));
+  HIPC(ctx, hipMemsetAsync(dout, 0, out_sz, s));
+  HIPC(ctx, launch_k_field_op(op, din, n, dout, s));
+  HIPC(ctx, hipMemcpyAsync(out, dout, out_sz, hipMemcpyDeviceToHost, s));
+  HIPC(ctx, hipStreamSynchronize(s));
+  return 0;
+}
+
 // Dependent Montgomery-product chain: `lanes` lanes (multiple of 64) x `iters` products.
 // ns_per_fpm = wall time / iters (per-lane latency); fpm_per_s = lanes * iters / time.
 extern "C" int bls_gpu_fpm_bench(bls_gpu_ctx* ctx, uint32_t lanes, uint32_t iters, double* ns_per_fpm,
@@ -2381,5 +2412,46 @@ extern "C" int bls_gpu_coop_probe(bls_gpu_ctx* ctx, const char* name, uint32_t b
     HIPC(ctx, hipMemcpyAsync(step_stamps, d_stamps, 8ull * (2 * pg.n + 1), hipMemcpyDeviceToHost, s));
     HIPC(ctx, hipStreamSynchronize(s));
   }
+  return 0;
+}
+
+// Test: program `name` of the loaded table run once on each of n_frames caller frames of
+// n_slots raw Fp values (12 little-endian words each); frames_out gets the raw frames
+// after the run, flags_out one zero-check flag word per frame.  n_slots must be the
+// program's frame size in the table (-2 otherwise: the constant bank sits behind it).
+extern "C" int bls_gpu_coop_run_test(bls_gpu_ctx* ctx, const char* name, const uint32_t* frames_in, uint32_t n_frames,
+                                     uint32_t n_slots, uint32_t* frames_out, uint32_t* flags_out) {
+  CTX_LOCK(ctx);
+  HIPC(ctx, hipSetDevice(ctx->device));
+  CoopProg pg{0, 0};
+  uint32_t frame = 0;
+  bool found = false;
+  for (size_t k = 0; name && k < ctx->coop_progs->size(); ++k)
+    if ((*ctx->coop_progs)[k].first == name) {
+      pg = (*ctx->coop_progs)[k].second;
+      frame = (*ctx->coop_frames)[k];
+      found = true;
+    }
+  if (!found) {
+    snprintf(ctx->err, sizeof(ctx->err), "no program %s", name ? name : "(null)");
+    return -1;
+  }
+  if (n_slots != frame || (frame != COOP_FRAME && frame != COOP_FRAME2 && frame != COOP_FRAME3)) {
+    snprintf(ctx->err, sizeof(ctx->err), "program %s has a frame of %u slots, not %u", name, frame, n_slots);
+    return -2;
+  }
+  if (n_frames == 0) return 0;
+  const std::string nm(name);
+  const bool w2 = nm.size() > 3 && nm.compare(nm.size() - 3, 3, "_w2") == 0;  // two-wavefront programs
+  const size_t fr_sz = sizeof(Fp) * (size_t)frame * n_frames, fr_al = (fr_sz + 255) & ~(size_t)255;
+  if (ensure_dev(ctx, 2 * fr_al + 4ull * n_frames)) return -1;
+  Fp *din = (Fp*)ctx->dev_ws, *dout = (Fp*)(ctx->dev_ws + fr_al);
+  uint32_t* dflags = (uint32_t*)(ctx->dev_ws + 2 * fr_al);
+  hipStream_t s = ctx->stream;
+  HIPC(ctx, hipMemcpyAsync(din, frames_in, fr_sz, hipMemcpyHostToDevice, s));
+  HIPC(ctx, launch_k_coop_run_test(ctx->coop, pg, frame, w2, din, n_frames, dout, dflags, s));
+  HIPC(ctx, hipMemcpyAsync(frames_out, dout, fr_sz, hipMemcpyDeviceToHost, s));
+  HIPC(ctx, hipMemcpyAsync(flags_out, dflags, 4ull * n_frames, hipMemcpyDeviceToHost, s));
+  HIPC(ctx, hipStreamSynchronize(s));
   return 0;
 }

@@ -316,3 +316,47 @@ hipError_t launch_k_coop_probe(const CoopEnv& env, CoopProg pg, uint32_t blocks,
   k_coop_probe<<<blocks, COOP_LANES, 0, s>>>(env.dev, pg, reps, sink, stamps);
   return hipGetLastError();
 }
+
+// Test (bls_gpu_coop_run_test): one block per caller frame runs program `pg` once and
+// writes the raw frame back -- lazy values as the interpreter left them, no fp_canon3 --
+// with the zero-check flag word.  FRAME_N is the program's own frame size: its ops
+// address the constants at slot FRAME_N + k (tools/gen_coop.py emit), so the bank must
+// sit directly behind a frame of exactly that size (k_coop_probe's one 640-slot layout
+// is good for timing only).  W wavefronts per frame (the *_w2 programs: 2).
+template <int FRAME_N, int W>
+__global__ __launch_bounds__(W * COOP_LANES) void k_coop_run_test(const CoopEnv* __restrict__ envp, CoopProg pg,
+                                                                  const Fp* __restrict__ in, Fp* __restrict__ out,
+                                                                  uint32_t* __restrict__ flags) {
+  const CoopEnv& env = *envp;
+  __shared__ CoopLdsN<FRAME_N> sh;
+  static_assert(offsetof(CoopLdsN<FRAME_N>, cbank) == FRAME_N * sizeof(Fp), "constant bank must follow the frame");
+  coop_stage_consts(env, sh.cbank);
+  const Fp* src = in + (size_t)blockIdx.x * FRAME_N;
+  for (int k = threadIdx.x; k < FRAME_N; k += W * COOP_LANES) lds_store_fp(sh.frame, k, src[k]);
+  if (threadIdx.x == 0) sh.flag = 0;
+  __syncthreads();
+  if (W == 1) coop_run(env, pg, sh.frame, sh.cbank, &sh.flag);
+  else coop_run2_t(env, pg, sh.frame, &sh.flag);
+  __syncthreads();
+  Fp* dst = out + (size_t)blockIdx.x * FRAME_N;
+  for (int k = threadIdx.x; k < FRAME_N; k += W * COOP_LANES) dst[k] = lds_load_fp(sh.frame, k);
+  if (threadIdx.x == 0) flags[blockIdx.x] = sh.flag;
+}
+
+template <int FRAME_N>
+static hipError_t launch_coop_run_test_n(const CoopEnv& env, CoopProg pg, bool w2, const Fp* in, uint32_t n_frames,
+                                         Fp* out, uint32_t* flags, hipStream_t s) {
+  if (w2) k_coop_run_test<FRAME_N, 2><<<n_frames, 2 * COOP_LANES, 0, s>>>(env.dev, pg, in, out, flags);
+  else k_coop_run_test<FRAME_N, 1><<<n_frames, COOP_LANES, 0, s>>>(env.dev, pg, in, out, flags);
+  return hipGetLastError();
+}
+
+hipError_t launch_k_coop_run_test(const CoopEnv& env, CoopProg pg, uint32_t frame, bool w2, const Fp* in,
+                                  uint32_t n_frames, Fp* out, uint32_t* flags, hipStream_t s) {
+  switch (frame) {
+    case COOP_FRAME: return launch_coop_run_test_n<COOP_FRAME>(env, pg, w2, in, n_frames, out, flags, s);
+    case COOP_FRAME2: return launch_coop_run_test_n<COOP_FRAME2>(env, pg, w2, in, n_frames, out, flags, s);
+    case COOP_FRAME3: return launch_coop_run_test_n<COOP_FRAME3>(env, pg, w2, in, n_frames, out, flags, s);
+    default: return hipErrorInvalidValue;
+  }
+}

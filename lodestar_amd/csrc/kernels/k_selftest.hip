@@ -2,6 +2,7 @@
 // the oracle) and a dependent chain of Montgomery products per lane (latency when
 // one wave runs alone, throughput when every CU is busy).
 #include "../launchers.hpp"
+#include "field_ops.hpp"
 
 using namespace bls;
 
@@ -29,4 +30,19 @@ hipError_t launch_k_fp_mul_test(const uint8_t* a, const uint8_t* b, uint32_t n, 
 hipError_t launch_k_fpm_chain(Fp* io, uint32_t lanes, uint32_t iters, hipStream_t s) {
   k_fpm_chain<<<lanes / BLS_BLOCK, BLS_BLOCK, 0, s>>>(io, iters);
   return hipGetLastError();
+}
+
+// the field-op self-test: this translation unit's kernels run the 32-bit column product,
+// kernels/k_selftest_d28.hip's the 28-bit-digit one (op bit FOP_D28_FLAG)
+int field_op_shape(uint32_t op, uint32_t* in_words, uint32_t* out_words) {
+  const uint32_t base = op & ~FOP_D28_FLAG;
+  if (base >= FOP_COUNT || (field_op_d28_only(base) && !(op & FOP_D28_FLAG))) return -2;
+  if (in_words) *in_words = (uint32_t)field_op_in_words(base);
+  if (out_words) *out_words = (uint32_t)field_op_out_words(base);
+  return 0;
+}
+hipError_t launch_k_field_op(uint32_t op, const uint32_t* in, uint32_t n, uint32_t* out, hipStream_t s) {
+  if (field_op_shape(op, nullptr, nullptr) != 0) return hipErrorInvalidValue;
+  if (op & FOP_D28_FLAG) return launch_k_field_op_d28(op & ~FOP_D28_FLAG, in, n, out, s);
+  return field_op_launch(op, in, n, out, s);
 }

@@ -70,6 +70,11 @@ hipError_t launch_k_sk_to_pk(const uint8_t* sks, uint32_t n, uint8_t* out48, hip
 hipError_t launch_k_sign(const uint8_t* sks, const uint8_t* msgs, uint32_t n, uint8_t* out96, hipStream_t s);
 hipError_t launch_k_mad_peak(uint64_t* out, uint32_t blocks, uint32_t iters, hipStream_t s);
 hipError_t launch_k_fp_mul_test(const uint8_t* a, const uint8_t* b, uint32_t n, uint8_t* out, hipStream_t s);
+// field-op self-test (kernels/field_ops.hpp): op = base id | FOP_D28_FLAG for the
+// 28-bit-digit translation unit; field_op_shape: record sizes in words, -2 unknown op
+int field_op_shape(uint32_t op, uint32_t* in_words, uint32_t* out_words);
+hipError_t launch_k_field_op(uint32_t op, const uint32_t* in, uint32_t n, uint32_t* out, hipStream_t s);
+hipError_t launch_k_field_op_d28(uint32_t op, const uint32_t* in, uint32_t n, uint32_t* out, hipStream_t s);
 hipError_t launch_k_fpm_chain(bls::Fp* io, uint32_t lanes, uint32_t iters, hipStream_t s);
 size_t kernel_probe_out_bytes(const char* name);
 hipError_t launch_kernel_probe(const char* name, void* out, uint32_t lanes, hipStream_t s);
@@ -90,6 +95,10 @@ hipError_t launch_k_indiv_simt(const bls::PipeBufs& b, const bls::GroupBufs& g, 
 #define BLS_FOLD1 4u  // sets per first-level k_fold group
 hipError_t launch_k_coop_probe(const bls::CoopEnv& env, bls::CoopProg pg, uint32_t blocks, uint32_t reps,
                                uint32_t* sink, uint64_t* stamps, hipStream_t s);
+// test: run program pg once on n_frames caller frames of `frame` slots (the program's own
+// frame size: 256, COOP_FRAME2 or COOP_FRAME3), two wavefronts per frame when w2
+hipError_t launch_k_coop_run_test(const bls::CoopEnv& env, bls::CoopProg pg, uint32_t frame, bool w2,
+                                  const bls::Fp* in, uint32_t n_frames, bls::Fp* out, uint32_t* flags, hipStream_t s);
 #define FPROD_FAN 16u
 hipError_t launch_k_fprod(const bls::Fp12* in, uint32_t n, bls::Fp12* out, int32_t* verdict,
                           const bls::CoopEnv& env, hipStream_t s);

@@ -402,6 +402,38 @@ class GpuContext:
         self._check(self.lib.bls_gpu_fp_mul_test(self._h, a, b, n, out), "bls_gpu_fp_mul_test")
         return out.raw[: 48 * n]
 
+    def field_op_shape(self, op: int) -> tuple[int, int]:
+        """(words per input record, words per output record) of a field-op self-test op"""
+        iw, ow = ctypes.c_uint32(), ctypes.c_uint32()
+        if self.lib.bls_gpu_field_op_shape(op, ctypes.byref(iw), ctypes.byref(ow)) != 0:
+            raise NativeError(f"bls_gpu_field_op_shape: unknown field op {op:#x}")
+        return iw.value, ow.value
+
+    def field_op_test(self, op: int, records: np.ndarray) -> np.ndarray:
+        """One field primitive per record on raw 32-bit words (include/lodestar_bls.h
+        bls_gpu_field_op_test): records is (n, in_words) uint32, the result (n, out_words)."""
+        iw, ow = self.field_op_shape(op)
+        rec = np.ascontiguousarray(records, dtype=np.uint32)
+        if rec.ndim != 2 or rec.shape[1] != iw:
+            raise ValueError(f"field op {op:#x} takes records of {iw} words, got {rec.shape}")
+        n = rec.shape[0]
+        out = np.zeros((max(n, 1), ow), dtype=np.uint32)
+        self._check(self.lib.bls_gpu_field_op_test(self._h, op, _ptr(rec), n, _ptr(out)), "bls_gpu_field_op_test")
+        return out[:n]
+
+    def coop_run_test(self, name: str, frames: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
+        """Program `name` of the loaded table run once per frame: frames is (n_frames,
+        n_slots, 12) uint32 raw Fp limbs; returns the raw frames after the run and the
+        zero-check flag word of each."""
+        fr = np.ascontiguousarray(frames, dtype=np.uint32)
+        if fr.ndim != 3 or fr.shape[2] != 12:
+            raise ValueError(f"frames must be (n_frames, n_slots, 12) uint32, got {fr.shape}")
+        out = np.zeros_like(fr)
+        flags = np.zeros(max(fr.shape[0], 1), dtype=np.uint32)
+        self._check(self.lib.bls_gpu_coop_run_test(self._h, name.encode(), _ptr(fr), fr.shape[0], fr.shape[1],
+                                                   _ptr(out), _ptr(flags)), "bls_gpu_coop_run_test")
+        return out, flags[: fr.shape[0]]
+
     def fpm_bench(self, lanes: int, iters: int) -> tuple[float, float]:
         ns, rate = ctypes.c_double(), ctypes.c_double()
         self._check(self.lib.bls_gpu_fpm_bench(self._h, lanes, iters, ctypes.byref(ns), ctypes.byref(rate)),

@@ -16,6 +16,7 @@
 #include "bls/hash_to_curve.hpp"
 #include "bls/pipeline.hpp"
 #include "bls/group_decode.hpp"
+#include "bls/selftest_ops.hpp"
 
 unsigned long long bls_fpm_counter = 0;
 unsigned long long bls_lz_norm_counter = 0;
@@ -495,38 +496,18 @@ void hs_lz_mul_raw(const int32_t* x, const int32_t* y, int32_t* out, int sqr) {
 }
 
 // canonical Fp (48 B big-endian, plain values) through the lazy forms and back, in
-// the order test_hostsim.py::test_lazy28_fp_ops expects (9 outputs of 48 B)
+// the order test_lazy28.py::test_lazy28_fp_ops expects (10 outputs of 48 B)
 void hs_lz_fp_ops(const uint8_t* a, const uint8_t* b, uint8_t* out) {
-  const auto x = lz_from_fp(rd_fp(a)), y = lz_from_fp(rd_fp(b));
-  const auto xy = lz_mul(x, y);
-  wr_fp(lz_to_fp(xy), out);                                       // a b
-  wr_fp(lz_to_fp(lz_sqr(x)), out + 48);                           // a^2
-  wr_fp(lz_to_fp(lz_add(x, y)), out + 96);                        // a + b
-  wr_fp(lz_to_fp(lz_sub(x, y)), out + 144);                       // a - b
-  wr_fp(lz_to_fp(lz_neg(xy)), out + 192);                         // -(a b)
-  wr_fp(lz_to_fp(lz_half(xy)), out + 240);                        // a b / 2
-  wr_fp(lz_to_fp(lz_norm(lz_sub(xy, lz_dbl(xy)))), out + 288);    // -(a b)
-  const auto s = lz_sub(lz_add(xy, xy), lz_mul(y, y));
-  wr_fp(lz_to_fp(lz_mul(s, lz_norm(lz_sub(y, x)))), out + 336);   // (2ab - b^2)(b - a)
-  wr_fp(lz_to_fp(x), out + 384);                                  // a (round trip)
-  // lz_reduce of a large signed combination: 4 (2ab - 7 b^2 - 7 a) (|value| up to 128 p)
-  const auto big = lz_sub(lz_sub(lz_add(xy, xy), lz_mulc<7>(lz_mul(y, y))), lz_mulc<7>(lz_mul(x, lz_one())));
-  const auto red = lz_reduce(lz_add(lz_add(big, big), lz_add(big, big)));
-  for (int k = 0; k < 13; ++k)
-    if (red.d[k] < 0 || red.d[k] > (int32_t)LZ_M28) out[0] ^= 0xFF;  // digits normalised
-  wr_fp(lz_to_fp(red), out + 432);
+  Fp r[10];
+  sf_lz_fp_ops(rd_fp(a), rd_fp(b), r);  // bls/selftest_ops.hpp: the body the device self-test runs too
+  for (int k = 0; k < 10; ++k) wr_fp(r[k], out + 48 * k);
 }
 
 // Fp2 (96 B: c0 || c1) through l2_*: out = mul, sqr, mul_xi, conj, sub, mul_fp (6 x 96 B)
 void hs_lz_fp2_ops(const uint8_t* a, const uint8_t* b, uint8_t* out) {
-  const auto x = l2_from_fp2(rd_fp2(a)), y = l2_from_fp2(rd_fp2(b));
-  const auto m = l2_mul(x, y);
-  wr_fp2(l2_to_fp2(m), out);
-  wr_fp2(l2_to_fp2(l2_sqr(x)), out + 96);
-  wr_fp2(l2_to_fp2(l2_mul_xi(m)), out + 192);
-  wr_fp2(l2_to_fp2(l2_conj(m)), out + 288);
-  wr_fp2(l2_to_fp2(l2_sub(m, l2_sqr(y))), out + 384);
-  wr_fp2(l2_to_fp2(l2_mul_fp(m, y.c0)), out + 480);
+  Fp2 r[6];
+  sf_lz_fp2_ops(rd_fp2(a), rd_fp2(b), r);
+  for (int k = 0; k < 6; ++k) wr_fp2(r[k], out + 96 * k);
 }
 
 }  // extern "C"

@@ -12,6 +12,8 @@ sys.path.insert(0, str(Path(__file__).resolve().parent.parent / "tools"))
 import gen_coop as GC  # noqa: E402
 from circuits import P, simulate  # noqa: E402
 
+from tests._coopsim import CoopTable  # noqa: E402
+
 
 @pytest.fixture(scope="module")
 def progs(coop_programs):
@@ -71,71 +73,6 @@ def test_fin_final_exponentiation(progs, oracle):
     assert get12(fr, GC.F) == oracle.final_exponentiation(f0, hard_multiple=3)
 
 
-def _run_binary(path, name, frame, n_consts):
-    """The emitted op table (gen_coop.emit) interpreted with coop.hpp coop_step's
-    semantics, lane by lane: kinds 1 (product), 2 (combination, or its part in a lane
-    group of the step's combination group size gl), 3 / 4 (part of a product's operand a
-    / b in a lane group of size gp: each half of the group sums one operand, every lane
-    multiplies), the group's first lane writes."""
-    import struct
-
-    raw = Path(path).read_bytes()
-    _, _, nc, nprog, _ = struct.unpack_from("<4sIIII", raw, 0)
-    off = 20
-    consts = [int.from_bytes(raw[off + 48 * k: off + 48 * (k + 1)], "little") for k in range(nc)]
-    off += 48 * nc
-    table = {}
-    for _ in range(nprog):
-        nm = raw[off: off + 32].rstrip(b"\0").decode()
-        table[nm] = struct.unpack_from("<IIII", raw, off + 32)
-        off += 48
-    first, n, n_slots, _ = table[name]
-    L = 128 if name.endswith("_w2") else 64  # two-wavefront programs: steps of 128 ops
-    R_INV = pow(1 << 384, -1, P)
-    cvals = [c * R_INV % P for c in consts]  # the bank is in Montgomery form
-    flag = 0
-    for s in range(n):
-        rec = first + s * (L // 64)
-        lanes = [struct.unpack_from("<HBBBBBB8H8H8h8h8x", raw, off + 80 * (64 * rec + ln)) for ln in range(L)]
-        # the per-step fields (max term counts, flags) are what every lane says
-        ma, mb, fl = lanes[0][4:7]
-        assert all(x[4:7] == (ma, mb, fl) for x in lanes)
-        assert ma == max((x[2] for x in lanes if x[1]), default=0)
-        assert mb == max((x[3] for x in lanes if x[1] == 1), default=0)
-        gp, gl = 1 << ((fl >> 2) & 3), 1 << ((fl >> 4) & 3)
-        lanes = [x[:4] + x[7:] for x in lanes]
-
-        def lin(refs, cfs, k):
-            return sum(cf * (frame[r] if r < n_slots else cvals[r - n_slots]) for r, cf in zip(refs[:k], cfs[:k])) % P
-
-        vals = []
-        for out, kind, na, nb, *rest in lanes:
-            ra, rb, ca, cb = rest[0:8], rest[8:16], rest[16:24], rest[24:32]
-            v = lin(ra, ca, na) if kind else 0
-            if kind == 1:
-                v = v * lin(rb, cb, nb) % P
-            vals.append(v)
-        res = list(vals)
-        for ln, (out, kind, *_r) in enumerate(lanes):
-            if kind == 2 and gl > 1:
-                base = ln & ~(gl - 1)
-                assert all(lanes[base + k][1] == 2 for k in range(gl) if lanes[base + k][1])
-                res[ln] = sum(vals[base: base + gl]) % P
-            elif kind in (3, 4):
-                base, h = ln & ~(gp - 1), gp // 2
-                assert [lanes[base + k][1] for k in range(gp)] == [3] * h + [4] * h
-                res[ln] = sum(vals[base: base + h]) * sum(vals[base + h: base + gp]) % P
-        for ln, (out, kind, *_r) in enumerate(lanes):
-            if kind == 0 or out == 0xFFFE:
-                continue
-            if out >= 0xFFF0:
-                if res[ln] == 0:
-                    flag |= 1 if out == 0xFFFF else 1 << (out - 0xFFF0)
-            else:
-                frame[out] = res[ln]
-    return flag
-
-
 def test_emitted_lane_groups_match_program(progs, tmp_path):
     """Steps with spare lanes spread their products and combinations over lane groups of
     2 or 4 (gen_coop.lane_entries); the table the device runs computes what the program
@@ -156,9 +93,33 @@ def test_emitted_lane_groups_match_program(progs, tmp_path):
     assert sum(gp == 2 for gp, _ in sizes) >= 10 and sum(gp == 4 for gp, _ in sizes) >= 3
     assert sum(gl == 4 for _, gl in sizes) >= 5
     rng = random.Random(7)
+    table = CoopTable.from_file(path)  # tests/_coopsim.py: coop.hpp coop_step's semantics, lane by lane
     for nm in names:
         fr = [rng.randrange(P) for _ in range(pg[nm].n_slots)]
         fr2 = list(fr)
         f1 = simulate(pg[nm], fr, consts)
-        f2 = _run_binary(path, nm, fr2, len(consts.vals))
+        f2 = table.run(nm, fr2)
         assert (fr, f1) == (fr2, f2), nm
+
+
+def test_emitted_accumulators_within_acc_reduce_bound(progs, tmp_path):
+    """acc_reduce's precondition (coop.hpp), which nothing else checks: the accumulator
+    it reduces is a sum of c x over values x < 3p, and the 2^20 p bias makes it
+    non-negative only while sum |c| * 3 <= 2^20; every |c| fits the int16 field with
+    room (|c| < 2^15).  Over every accumulator of the emitted table: one lane's operand,
+    or the operands the DPP butterflies add together (the gl lanes of a combination
+    group, each half of a product group)."""
+    pg, consts = progs
+    path = tmp_path / "all.bin"
+    GC.emit(list(pg.values()), consts, path)
+    table = CoopTable.from_file(path)
+    assert set(table.programs) == set(pg)
+    n_acc, worst_sum, worst_c = 0, 0, 0
+    for nm in table.programs:
+        for cs in table.accumulators(nm):
+            n_acc += 1
+            assert all(abs(c) < 1 << 15 for c in cs), (nm, cs)
+            assert 3 * sum(abs(c) for c in cs) <= 1 << 20, (nm, cs)
+            worst_sum = max(worst_sum, sum(abs(c) for c in cs))
+            worst_c = max([worst_c] + [abs(c) for c in cs])
+    assert n_acc > 10000 and worst_c > 1  # (the real table: largest sum |c| 147, largest |c| 144)

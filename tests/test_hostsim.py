@@ -1,7 +1,18 @@
 """The HIP kernels' math compiled for the CPU (tests/native/hostsim.cpp) against the
-oracle and the golden fixtures -- runs without a GPU.  The device build differs only
-in fp_mul (the 28-bit-digit product, checked here on raw limbs by
-test_fp_mul_d28_lazy, and on the GPU by tests/test_gpu_parity.py)."""
+oracle and the golden fixtures -- runs without a GPU.
+
+This is the PORTABLE branch of bls/*.hpp.  The device build replaces, behind
+__HIP_DEVICE_COMPILE__ or in device-only headers: the carry chains of fp_add, fp_sub,
+fp_add_nr, fp_sub_nr, fp_reduce_once, fp_reduce_2p, fp_canon3 and the 13-limb
+accumulator (inline asm, bls/carry_asm.hpp; 64-bit words with __int128 here); the
+multiply-adds of fp2_mul_d28 / fp2_sqr_d28 / fp_redc_d28<true> (ordered
+v_mad_u64_u32 / v_mad_i64_i32, plain C here); fp_mul / fp_sqr themselves (the 28-bit-digit
+or the 32-bit column product by translation unit; the 64-bit product here -- the digit
+product is checked here on raw limbs by test_fp_mul_d28_lazy); and the interpreter's
+arithmetic in bls/coop.hpp (coop_lin_acc, acc_reduce, the DPP butterflies,
+fp_is_zero_lazy), which has no host counterpart.  Those run, primitive by primitive and
+program by program, on the GPU in tests/test_gpu_field_ops.py, on the vectors of
+tests/_fieldvec.py (which tests/test_fieldvec.py checks against this harness)."""
 from __future__ import annotations
 
 import ctypes

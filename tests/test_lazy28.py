@@ -8,57 +8,23 @@ import ctypes
 import random
 
 from tests._codec import P, b48, fp
+from tests._fieldvec import digits_value as _val, lz_raw_cases
 
 M28 = (1 << 28) - 1
 RP_INV = pow(2, -392, P)
-
-
-def _val(d) -> int:
-    return sum(int(x) << (28 * k) for k, x in enumerate(d))
 
 
 def _arr(d):
     return (ctypes.c_int32 * 14)(*d)
 
 
-def _signed_digits(v: int, rng, dmax: int) -> list[int]:
-    """A signed digit vector of value v (any sign) with |digits| pushed up to dmax (moving
-    multiples of 2^28 between neighbouring digits), so the product sees unnormalised,
-    mixed-sign operands."""
-    d = [0] * 14
-    m = abs(v)
-    for k in range(13):
-        d[k] = (m >> (28 * k)) & M28
-    d[13] = m >> (28 * 13)
-    if v < 0:
-        d = [-x for x in d]
-    for k in range(13):
-        # move t units of digit k+1 into digit k (value unchanged)
-        for _ in range(3):
-            t = rng.randint(-4, 4)
-            nk, nk1 = d[k] + t * (1 << 28), d[k + 1] - t
-            if abs(nk) <= dmax and abs(nk1) <= dmax:
-                d[k], d[k + 1] = nk, nk1
-    assert _val(d) == v and max(abs(x) for x in d) <= dmax
-    return d
-
-
 def test_lazy28_raw_product_bounds(hostsim):
     """lz_mul_core / lz_sqr_core on signed digits: x y / 2^392 mod p, digits 0..12 of the
     output in [0, 2^28), |value| < p + |x y| / 2^392, for operands at the largest digits
     lz_mul_fits admits (|digit| ~2^29.5 each side) and large magnitudes of either sign."""
-    rng = random.Random(392)
     out = (ctypes.c_int32 * 14)()
-    cases = []
-    for _ in range(300):
-        vx = rng.randrange(1 << rng.choice((10, 200, 381, 384, 388))) * rng.choice((1, -1))
-        vy = rng.randrange(1 << rng.choice((10, 200, 381, 384, 388))) * rng.choice((1, -1))
-        cases.append((vx, vy))
-    cases += [(0, 0), (P - 1, P - 1), (-(2 * P - 1), 2 * P - 1), (256 * P - 1, -9 * P), ((1 << 388) - 1, P)]
-    dmax = int(2 ** 29.5)
-    for vx, vy in cases:
-        x = _signed_digits(vx, rng, dmax)
-        y = _signed_digits(vy, rng, dmax)
+    # (the case generator lives in tests/_fieldvec.py: the device self-test runs the same operands)
+    for x, y, vx, vy in lz_raw_cases():
         for sqr in (0, 1):
             yv = vx if sqr else vy
             hostsim.hs_lz_mul_raw(_arr(x), _arr(x if sqr else y), out, sqr)
