@@ -193,6 +193,45 @@ int bls_gpu_verify(bls_gpu_ctx* ctx, const bls_batch* batch, int32_t* verdicts, 
 int bls_gpu_verify_many(bls_gpu_ctx* ctx, const bls_batch* batches, uint32_t n_batches, int32_t* verdicts,
                         bls_stats* stats);
 
+/* IBlsVerifier.verifySignatureSetsSameMessage(sets, message) -> boolean[]: jobs of
+ * {publicKey, signature} pairs that all sign ONE root (unaggregated gossip
+ * attestations).  The reference checks a job with aggregateWithRandomness -- one
+ * pairing equation e(sum r_i pk_i, H(m)) e(-g1, sum r_i sig_i) == 1 -- and verifies
+ * every set on its own when that fails.  Several jobs go in one call (the pool handing
+ * a context every same-message job that is ready).  Job j owns sets
+ * [job_set_offsets[j], job_set_offsets[j + 1]), each >= 1 and <= BLS_SAME_MSG_MAX_JOB
+ * sets; public keys are device-table indices. */
+#define BLS_SAME_MSG_MAX_JOB 4096u
+typedef struct bls_same_msg_batch {
+  uint32_t n_jobs, n_sets;
+  const uint32_t* job_set_offsets; /* n_jobs + 1, from 0 to n_sets */
+  const uint8_t* messages;         /* n_jobs * 32: one signing root per job */
+  const uint32_t* pk_indices;      /* n_sets: one device-table index per set */
+  const uint8_t* signatures;       /* n_sets * 96 compressed G2 */
+  const uint8_t* seed;             /* 32 bytes or NULL, as in bls_batch */
+} bls_same_msg_batch;
+
+/* set_verdicts: n_sets int32.
+ *   - A job is one random-scalar batch over all of its sets, whatever its size (it is
+ *     not chunked at 16); set i of the call draws its scalar from the seed at index i.
+ *     Two Miller loops and one final exponentiation per job, one hash-to-curve per
+ *     distinct root (two jobs carrying the same root share H(m) and stay two batches).
+ *   - A passing job gives every set 1.
+ *   - A job fails when its check fails or any of its sets has a decode or group error;
+ *     each of its sets then gets the verdict bls_gpu_verify gives a one-set request of
+ *     that key index, root and signature: 1, 0 or -code under the one-set rules (an
+ *     index past the table BLS_CODE_BAD_ENCODING, an infinity signature
+ *     BLS_CODE_ZERO_SIGNATURE), found by the individual pass and its group tests.
+ *   - A 1-set job is verified on its own directly.
+ * n_jobs == 0 returns 0 and writes nothing; an empty or oversized job, offsets that do
+ * not run monotonically from 0 to n_sets, or a NULL pointer where one is needed
+ * return -2.  stats (nullable): n_chunks = jobs batched (>= 2 sets), batch_retries =
+ * failed jobs, batch_sigs_success = sets of passing jobs, n_ml_units = one per batched
+ * job, n_unique_msgs = distinct roots in the call, n_individual = sets verified on
+ * their own. */
+int bls_gpu_verify_same_message(bls_gpu_ctx* ctx, const bls_same_msg_batch* batch, int32_t* set_verdicts,
+                                bls_stats* stats);
+
 /* Sharded call across GPUs (north_star "each GPU reduces its shard to
  * an Fp12 partial, the partials are combined over RCCL/xGMI, and one final
  * exponentiation follows").  The reference verifies one call as ONE random-scalar

@@ -33,6 +33,18 @@
  * table loaded with loadPubkeys, i.e. index2pubkey) or {pubkey: Uint8Array(96)}
  * (uncompressed affine, the worker wire format of index.ts:126), plus
  * {signingRoot: Uint8Array(32), signature: Uint8Array}.
+ *
+ * verifySignatureSetsSameMessage(sets, message, opts) -> Promise<boolean[]> (the
+ * reference's IBlsVerifier method for unaggregated gossip attestations): sets are
+ * {publicKey: index | Uint8Array, signature}, all signing `message`.  The table-index sets
+ * of a call form one same-message job, queued as its own job kind; an idle context takes
+ * every same-message job that is ready (up to maxSetsPerCall sets) in ONE
+ * addon.verifySameMessage call (bls_gpu_verify_same_message), where each job is one
+ * random-scalar batch over all its sets -- the reference's aggregateWithRandomness -- and
+ * a failing job's sets are verified on their own.  A set's verdict is true iff its code is
+ * 1 (an error code is false).  Sets whose publicKey is not a table index (raw 96-byte
+ * keys) do not enter the batch: each goes through the existing path as a one-set
+ * batchable request.
  * Plain CommonJS so it runs on the Node in this image (v12); the TypeScript
  * version is the same code with the reference's types.
  */
@@ -152,6 +164,31 @@ function packRequests(jobs, seed) {
           seed: seed || null};
 }
 
+/** Pack same-message jobs ({message, indices, signatures}) into the SoA request of
+ * addon.verifySameMessage (bls_same_msg_batch). */
+function packSameMessage(jobs, seed) {
+  let nSets = 0;
+  for (let j = 0; j < jobs.length; j++) nSets += jobs[j].indices.length;
+  const jobSetOffsets = new Uint32Array(jobs.length + 1);
+  const messages = Buffer.allocUnsafe(Math.max(32 * jobs.length, 1));
+  const pkIndices = new Uint32Array(Math.max(nSets, 1));
+  const signatures = Buffer.allocUnsafe(Math.max(96 * nSets, 1));
+  let k = 0;
+  for (let j = 0; j < jobs.length; j++) {
+    const job = jobs[j];
+    if (job.message.length !== 32) throw Error("signing roots are 32 bytes");
+    messages.set(job.message, 32 * j);
+    for (let i = 0; i < job.indices.length; i++) {
+      if (job.signatures[i].length !== 96) throw Error("signatures are 96 bytes (compressed G2)");
+      pkIndices[k] = job.indices[i];
+      signatures.set(job.signatures[i], 96 * k);
+      k++;
+    }
+    jobSetOffsets[j + 1] = k;
+  }
+  return {jobSetOffsets, messages, pkIndices, signatures, seed: seed || null};
+}
+
 /** Contiguous [beg, end) shards of n sets over `parts` devices, sizes differing by at
  * most one (lodestar_amd/shard.py shard_bounds): set i keeps its call index, so its
  * random scalar is the same whichever device holds it. */
@@ -264,6 +301,7 @@ class GpuBlsVerifier {
     }
     this.jobs = []; // queue: jobs[jobsHead..] are pending
     this.jobsHead = 0;
+    this.smJobs = []; // same-message jobs ({message, indices, signatures, resolve, reject}), their own kind
     this.runScheduled = false;
     this.bufJobs = []; // batchable jobs waiting for > 32 sigs or 100 ms (index.ts:262-279)
     this.bufSigs = 0;
@@ -328,6 +366,52 @@ class GpuBlsVerifier {
       return this._splitCall(sets);
     }
     return this._queueCall(sets, batchable);
+  }
+
+  /**
+   * IBlsVerifier.verifySignatureSetsSameMessage(sets, message, opts) -> Promise<boolean[]>:
+   * sets = [{publicKey: index | Uint8Array(96), signature}], all signing `message`; one
+   * boolean per set, true iff the set is valid (see the header comment).
+   */
+  verifySignatureSetsSameMessage(sets, message, opts) {
+    void opts; // (the reference's {priority}: same-message jobs are taken before the queue)
+    const n = sets.length;
+    if (n === 0) return Promise.resolve([]);
+    if (this.closed) return Promise.reject(Error("QUEUE_ABORTED"));
+    if (this.ctxs.length === 0 && this.initErrors.length > 0) return Promise.reject(this.initErrors[0]);
+    const out = new Array(n);
+    const parts = [];
+    const inJob = [];
+    for (let k = 0; k < n; k++) {
+      const s = sets[k];
+      if (typeof s.publicKey === "number" && s.signature.length === 96) {
+        inJob.push(k);
+      } else {
+        // not a table index: the existing path, as a one-set batchable request (a set that
+        // errors is false, as the reference maps a throwing set)
+        const set = typeof s.publicKey === "number"
+          ? {pubkeyIndices: [s.publicKey], signingRoot: message, signature: s.signature}
+          : Array.isArray(s.publicKey)
+            ? {pubkeyIndices: s.publicKey, signingRoot: message, signature: s.signature}
+            : {pubkey: s.publicKey, signingRoot: message, signature: s.signature};
+        parts.push(this._queue(true, [set]).then((v) => { out[k] = v === true; }, (e) => {
+          if (e && e.message === "QUEUE_ABORTED") throw e;
+          out[k] = false;
+        }));
+      }
+    }
+    if (inJob.length > 0) {
+      parts.push(new Promise((resolve, reject) => {
+        this.smJobs.push({
+          message, indices: inJob.map((k) => sets[k].publicKey), signatures: inJob.map((k) => sets[k].signature),
+          resolve, reject, addedTimeMs: this.metrics ? Date.now() : 0,
+        });
+        this._scheduleRun();
+      }).then((codes) => {
+        for (let i = 0; i < inJob.length; i++) out[inJob[i]] = codes[i] === 1;
+      }));
+    }
+    return Promise.all(parts).then(() => out);
   }
 
   /** The reference's path for a call: chunkifyMaximizeChunkSize(sets, 128) jobs, AND-ed. */
@@ -436,7 +520,8 @@ class GpuBlsVerifier {
     this.closed = true;
     if (this.bufTimer) clearTimeout(this.bufTimer);
     this.bufTimer = null;
-    const pending = this.jobs.slice(this.jobsHead).concat(this.bufJobs);
+    const pending = this.jobs.slice(this.jobsHead).concat(this.bufJobs, this.smJobs);
+    this.smJobs = [];
     const pinned = [].concat(...this.pinned);
     this.jobs = [];
     this.jobsHead = 0;
@@ -547,7 +632,7 @@ class GpuBlsVerifier {
           this._startPinned(ctx, this.pinned[s].shift());
         }
       }
-      if (this.jobsHead >= this.jobs.length) return;
+      if (this.jobsHead >= this.jobs.length && this.smJobs.length === 0) return;
       let ctx = null;
       let best = Infinity;
       for (let s = 0; s < this.nSlots; s++) {
@@ -559,7 +644,8 @@ class GpuBlsVerifier {
         }
       }
       if (ctx === null) return;
-      this._startJobs(ctx);
+      if (this.smJobs.length > 0) this._startSameMessageJobs(ctx);
+      else this._startJobs(ctx);
     }
   }
 
@@ -596,6 +682,64 @@ class GpuBlsVerifier {
         this._dispatch();
       }
     );
+  }
+
+  /** Every same-message job that is ready, up to maxSetsPerCall sets, in one
+   * addon.verifySameMessage call; each job resolves to its sets' codes. */
+  _startSameMessageJobs(ctx) {
+    const jobs = [];
+    let total = 0;
+    while (this.smJobs.length > 0 && total < this.maxSetsPerCall) {
+      const j = this.smJobs.shift();
+      jobs.push(j);
+      total += j.indices.length;
+    }
+    const weight = total; // setWeight of a single-key set is 1
+    const tp = this.metrics && this.metrics.blsThreadPool;
+    this.stats.jobGroupsStarted += 1;
+    this.stats.jobsStarted += jobs.length;
+    this.stats.sigSetsStarted += total;
+    const st = this.slotStats[ctx.slot];
+    st.calls++;
+    st.sets += total;
+    st.weight += weight;
+    if (tp) {
+      const now = Date.now();
+      for (const j of jobs) tp.jobWaitTime.observe((now - j.addedTimeMs) / 1000);
+      tp.totalJobsGroupsStarted.inc(1);
+      tp.totalJobsStarted.inc(jobs.length);
+      tp.totalSigSetsStarted.inc(total);
+    }
+    this.slotLoad[ctx.slot] += weight;
+    const fail = (e) => {
+      this.slotLoad[ctx.slot] -= weight;
+      for (const j of jobs) j.reject(e);
+      if (tp) tp.errorJobsSignatureSetsCount.inc(total);
+      this._dispatch();
+    };
+    let req;
+    try {
+      req = packSameMessage(jobs);
+    } catch (e) {
+      fail(e);
+      return;
+    }
+    this._run(ctx, () => this.addon.verifySameMessage(ctx.handle, req)).then((verdicts) => {
+      this.slotLoad[ctx.slot] -= weight;
+      this.stats.batchRetries += verdicts.batchRetries || 0;
+      this.stats.batchSigsSuccess += verdicts.batchSigsSuccess || 0;
+      if (tp) {
+        tp.batchRetries.inc(verdicts.batchRetries || 0);
+        tp.batchSigsSuccess.inc(verdicts.batchSigsSuccess || 0);
+        tp.successJobsSignatureSetsCount.inc(total);
+      }
+      let k = 0;
+      for (const j of jobs) {
+        j.resolve(verdicts.subarray(k, k + j.indices.length));
+        k += j.indices.length;
+      }
+      this._dispatch();
+    }, fail);
   }
 
   /** Take queued jobs of one pubkey form (table indices or raw bytes) for one call and
@@ -706,6 +850,7 @@ module.exports = {
   GpuBlsVerifier,
   chunkifyMaximizeChunkSize,
   packRequests,
+  packSameMessage,
   shardBounds,
   setWeight,
   getAggregatedPubkeysCount,

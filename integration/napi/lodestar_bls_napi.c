@@ -14,6 +14,10 @@
  *          errClass, errIndex}>   (bls_gpu_partial: a shard of a call split across devices;
  *          request.seed must hold the call's 32-byte seed)
  *   finalCheck(handle, Uint8Array partials (576 B each)) -> Promise<boolean>   (bls_gpu_final_check)
+ *   verifySameMessage(handle, {jobSetOffsets, messages, pkIndices, signatures, seed?})
+ *          -> Promise<Int32Array set verdicts>   (bls_gpu_verify_same_message: jobs of table-index
+ *          sets that sign one root each, IBlsVerifier.verifySignatureSetsSameMessage; the array
+ *          also carries nChunks = jobs batched and nIndividual = sets verified on their own)
  *   close(handle)
  *
  * The verdict array carries the worker's BlsWorkResult bookkeeping (types.ts:26-38) as
@@ -194,13 +198,14 @@ static napi_value js_load_pubkeys(napi_env env, napi_callback_info info) {
   return out;
 }
 
-enum { JOB_VERIFY = 0, JOB_PARTIAL = 1, JOB_FINAL = 2 };
+enum { JOB_VERIFY = 0, JOB_PARTIAL = 1, JOB_FINAL = 2, JOB_SAME_MSG = 3 };
 
 typedef struct {
   int kind;
   bls_handle* h;
   bls_gpu_ctx* ctx;
   bls_batch batch;
+  bls_same_msg_batch same;  /* JOB_SAME_MSG */
   napi_ref keep;          /* the request object: keeps the input buffers alive */
   napi_ref keep_handle;   /* the handle object: no finalizer while the job is out */
   int32_t* verdicts;
@@ -248,6 +253,8 @@ static void verify_execute(napi_env env, void* data) {
     j->rc = bls_gpu_partial(j->ctx, &j->batch, j->base, j->part, &j->status, j->err_info, &j->stats);
   else if (j->kind == JOB_FINAL)
     j->rc = bls_gpu_final_check(j->ctx, j->partials, j->n_partials, &j->verdict);
+  else if (j->kind == JOB_SAME_MSG)
+    j->rc = bls_gpu_verify_same_message(j->ctx, &j->same, j->verdicts, &j->stats);
   else
     j->rc = bls_gpu_verify(j->ctx, &j->batch, j->verdicts, &j->stats);
   j->t_end_ns = mono_ns();
@@ -259,7 +266,9 @@ static void verify_complete(napi_env env, napi_status status, void* data) {
     napi_value msg, err;
     char text[640];
     snprintf(text, sizeof(text), "%s failed (rc %d, status %d): %s",
-             j->kind == JOB_PARTIAL ? "bls_gpu_partial" : (j->kind == JOB_FINAL ? "bls_gpu_final_check" : "bls_gpu_verify"),
+             j->kind == JOB_PARTIAL ? "bls_gpu_partial"
+             : j->kind == JOB_FINAL ? "bls_gpu_final_check"
+             : j->kind == JOB_SAME_MSG ? "bls_gpu_verify_same_message" : "bls_gpu_verify",
              j->rc, (int)status,
              j->rc ? bls_gpu_last_error(j->ctx) : "cancelled");
     napi_create_string_utf8(env, text, NAPI_AUTO_LENGTH, &msg);
@@ -296,11 +305,18 @@ static void verify_complete(napi_env env, napi_status status, void* data) {
   } else {
     napi_value ab, out;
     void* dst;
-    uint32_t n = j->batch.n_reqs;
+    uint32_t n = j->kind == JOB_SAME_MSG ? j->same.n_sets : j->batch.n_reqs;
     napi_create_arraybuffer(env, 4 * (size_t)(n ? n : 1), &dst, &ab);
     memcpy(dst, j->verdicts, 4 * (size_t)n);
     napi_create_typedarray(env, napi_int32_array, n, ab, 0, &out);
     attach_stats(env, out, &j->stats, j->t_start_ns, j->t_end_ns);
+    if (j->kind == JOB_SAME_MSG) {
+      napi_value v;
+      napi_create_uint32(env, j->stats.n_chunks, &v);
+      napi_set_named_property(env, out, "nChunks", v);
+      napi_create_uint32(env, j->stats.n_individual, &v);
+      napi_set_named_property(env, out, "nIndividual", v);
+    }
     napi_resolve_deferred(env, j->deferred, out);
   }
   napi_delete_reference(env, j->keep);
@@ -387,6 +403,47 @@ static napi_value js_verify(napi_env env, napi_callback_info info) {
   j->kind = JOB_VERIFY;
   j->batch = b;
   j->verdicts = (int32_t*)calloc(b.n_reqs ? b.n_reqs : 1, 4);
+  return queue_job(env, h, j, argv[0], argv[1]);
+}
+
+/* verifySameMessage(handle, {jobSetOffsets, messages, pkIndices, signatures, seed?}) ->
+ * Promise<Int32Array>: bls_gpu_verify_same_message on a libuv worker, one verdict per set.
+ * The buffer sizes are checked here; the library checks the offsets themselves (an empty
+ * job rejects with its -2 and message). */
+static napi_value js_verify_same_message(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  bls_handle* h = argc >= 2 ? get_handle(env, argv[0]) : NULL;
+  if (!h) {
+    napi_throw_type_error(env, NULL, "verifySameMessage(handle, request): no live handle (closed?)");
+    return NULL;
+  }
+  void *jo, *msg, *pki, *sig, *seed;
+  size_t njo, nmsg, npki, nsig, nseed;
+  if (prop(env, argv[1], "jobSetOffsets", &jo, &njo) || prop(env, argv[1], "messages", &msg, &nmsg) ||
+      prop(env, argv[1], "pkIndices", &pki, &npki) || prop(env, argv[1], "signatures", &sig, &nsig) ||
+      prop(env, argv[1], "seed", &seed, &nseed) || njo < 4 || !jo) {
+    napi_throw_type_error(env, NULL, "verifySameMessage: bad request object");
+    return NULL;
+  }
+  const uint32_t n_jobs = (uint32_t)(njo / 4 - 1);
+  const uint32_t n_sets = ((const uint32_t*)jo)[n_jobs];
+  if (nmsg < 32 * (size_t)n_jobs || npki < 4 * (size_t)n_sets || nsig < 96 * (size_t)n_sets) {
+    napi_throw_range_error(env, NULL, "verifySameMessage: a buffer is shorter than n_jobs / n_sets require "
+                                      "(messages 32 B per job, pkIndices 4 B and signatures 96 B per set)");
+    return NULL;
+  }
+  verify_job* j = (verify_job*)calloc(1, sizeof(verify_job));
+  j->kind = JOB_SAME_MSG;
+  j->same.n_jobs = n_jobs;
+  j->same.n_sets = n_sets;
+  j->same.job_set_offsets = (const uint32_t*)jo;
+  j->same.messages = (const uint8_t*)msg;
+  j->same.pk_indices = (const uint32_t*)pki;
+  j->same.signatures = (const uint8_t*)sig;
+  j->same.seed = nseed >= 32 ? (const uint8_t*)seed : NULL;
+  j->verdicts = (int32_t*)calloc(n_sets ? n_sets : 1, 4);
   return queue_job(env, h, j, argv[0], argv[1]);
 }
 
@@ -537,6 +594,7 @@ static napi_value module_init(napi_env env, napi_value exports) {
       {"sszRoots", NULL, js_ssz_roots, NULL, NULL, NULL, napi_default, NULL},
       {"partial", NULL, js_partial, NULL, NULL, NULL, napi_default, NULL},
       {"finalCheck", NULL, js_final_check, NULL, NULL, NULL, napi_default, NULL},
+      {"verifySameMessage", NULL, js_verify_same_message, NULL, NULL, NULL, napi_default, NULL},
   };
   napi_define_properties(env, exports, sizeof(d) / sizeof(d[0]), d);
   return exports;

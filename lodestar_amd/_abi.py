@@ -48,6 +48,7 @@ SYMBOLS = (
     "bls_gpu_load_pubkeys",
     "bls_gpu_verify",
     "bls_gpu_verify_many",
+    "bls_gpu_verify_same_message",
     "bls_gpu_aggregate_pubkeys",
     "bls_gpu_validate_pubkeys",
     "bls_gpu_partial",
@@ -123,6 +124,23 @@ class BlsBatch(ctypes.Structure):
     ]
 
 
+class BlsSameMsgBatch(ctypes.Structure):
+    """bls_same_msg_batch: jobs of (table index, signature) sets that sign one root each"""
+
+    _fields_ = [
+        ("n_jobs", ctypes.c_uint32),
+        ("n_sets", ctypes.c_uint32),
+        ("job_set_offsets", ctypes.c_void_p),
+        ("messages", ctypes.c_void_p),
+        ("pk_indices", ctypes.c_void_p),
+        ("signatures", ctypes.c_void_p),
+        ("seed", ctypes.c_void_p),
+    ]
+
+
+SAME_MSG_MAX_JOB = 4096  # BLS_SAME_MSG_MAX_JOB
+
+
 class BlsAdmission(ctypes.Structure):
     _fields_ = [
         ("contexts_normal", ctypes.c_uint32),
@@ -171,6 +189,8 @@ def bind(lib: ctypes.CDLL) -> ctypes.CDLL:
         lib.bls_gpu_verify.restype = i32
         lib.bls_gpu_verify_many.argtypes = [vp, ctypes.POINTER(BlsBatch), u32, vp, ctypes.POINTER(BlsStats)]
         lib.bls_gpu_verify_many.restype = i32
+        lib.bls_gpu_verify_same_message.argtypes = [vp, ctypes.POINTER(BlsSameMsgBatch), vp, ctypes.POINTER(BlsStats)]
+        lib.bls_gpu_verify_same_message.restype = i32
         lib.bls_gpu_validate_pubkeys.argtypes = [vp, vp, u32, u32, vp]
         lib.bls_gpu_validate_pubkeys.restype = i32
         lib.bls_gpu_partial.argtypes = [vp, ctypes.POINTER(BlsBatch), u32, vp, vp, vp, ctypes.POINTER(BlsStats)]

@@ -248,6 +248,25 @@ def build_hostsim(verbose: bool = True) -> Path:
     return out
 
 
+def build_smsum_host(verbose: bool = True, out: Path | None = None, extra: list[str] | None = None) -> Path:
+    """CPU restatement of k_smsum and the same-message plan (tests/native/smsum_host.cpp), a
+    stand-alone program for tests/; `extra` compiler flags (a sanitizer build) need their
+    own `out`."""
+    src = ROOT / "tests" / "native" / "smsum_host.cpp"
+    out = out or ROOT / "tests" / "native" / "smsum_host"
+    key = hashlib.sha256((_headers_digest() + " ".join(extra or [])).encode() + src.read_bytes()).hexdigest()[:16]
+    stamp = out.with_suffix(".stamp")
+    if out.exists() and stamp.exists() and stamp.read_text() == key:
+        return out
+    cmd = ["g++", "-O2", "-std=c++17", *(extra or []), "-I", str(CSRC), "-I", str(ROOT / "include"), "-o", str(out),
+           str(src)]
+    if verbose:
+        print("[build]", " ".join(cmd), flush=True)
+    subprocess.run(cmd, check=True)
+    stamp.write_text(key)
+    return out
+
+
 def build_cpu_baseline(verbose: bool = True) -> Path:
     """The C++ CPU baseline under oracle/cpu (benchmark / test infrastructure, "not
     blst"; oracle/cpu/bls_cpu.cpp), next to its source: bench.py's cpu_baseline leg
@@ -288,4 +307,5 @@ if __name__ == "__main__":
     build(jobs=int(sys.argv[1]) if len(sys.argv) > 1 else None)
     build_napi()
     build_hostsim()
+    build_smsum_host()
     build_cpu_baseline()

@@ -511,6 +511,44 @@ static inline void plan_batch(const bls_batch* in, BatchPlan& p) {
   chunkify_maximize_chunk_size((uint32_t)batchable.size(), 16, p.chunk_off);
 }
 
+// Plan of one bls_gpu_verify_same_message call over the verify pass: every set is a
+// one-set batchable request (request index == set index, so a failing job's fallback gives
+// the one-set path's verdicts), every job of >= 2 sets is a caller-defined chunk -- ONE
+// random-scalar batch whatever its size, not chunked at 16 -- and a 1-set job is a request
+// verified on its own directly.
+struct SameMsgPlan {
+  BatchPlan plan;
+};
+
+// shape checks of the caller's batch: nullptr, or what is wrong (the call returns -2)
+static inline const char* check_same_message(const bls_same_msg_batch* in, const int32_t* set_verdicts) {
+  if (!in->job_set_offsets || !in->messages || !in->pk_indices || !in->signatures || !set_verdicts)
+    return "a required pointer is NULL";
+  if (in->job_set_offsets[0] != 0 || in->job_set_offsets[in->n_jobs] != in->n_sets)
+    return "job_set_offsets must run from 0 to n_sets";
+  for (uint32_t j = 0; j < in->n_jobs; ++j) {
+    const uint32_t beg = in->job_set_offsets[j], end = in->job_set_offsets[j + 1];
+    if (end <= beg || end > in->n_sets) return "empty job or offsets not monotone";
+    if (end - beg > BLS_SAME_MSG_MAX_JOB) return "job of more than BLS_SAME_MSG_MAX_JOB sets";
+  }
+  return nullptr;
+}
+
+static inline void plan_same_message(const bls_same_msg_batch* in, SameMsgPlan& p) {
+  p.plan.chunk_off.assign(1, 0);
+  p.plan.chunk_reqs.clear();
+  p.plan.nonbatch_reqs.clear();
+  for (uint32_t j = 0; j < in->n_jobs; ++j) {
+    const uint32_t beg = in->job_set_offsets[j], end = in->job_set_offsets[j + 1];
+    if (end - beg == 1) {
+      p.plan.nonbatch_reqs.push_back(beg);
+      continue;
+    }
+    for (uint32_t i = beg; i < end; ++i) p.plan.chunk_reqs.push_back(i);
+    p.plan.chunk_off.push_back((uint32_t)p.plan.chunk_reqs.size());
+  }
+}
+
 // Signing-root dedup for stage_pre: uniq = the first set of each distinct 32-byte
 // root (in set order), rep[i] = that first set for set i.  Committee-shared roots
 // (~512 attesters per root) then pay hash_to_field + SSWU once.

@@ -17,6 +17,9 @@
 //   k_indiv  failed chunks' requests + non-batchable requests          (wavefront)
 // All kernels of a call run on the context's stream; the host waits twice
 // (chunk verdicts, final verdicts).
+// bls_gpu_verify_same_message runs the same pass with a plan of its own (every job one
+// chunk and one Miller-loop unit) on the aggregated-signature path, its sums by k_smsum
+// (kernels/k_smsg.hip); DESIGN.md section 3 "Same-message calls".
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
 #include <stdio.h>
@@ -1175,6 +1178,27 @@ static int check_batch(bls_gpu_ctx* ctx, const bls_batch* in, const char* what) 
   return 0;
 }
 
+// The Miller-loop units of a same-message call (bls/pipeline.hpp plan_same_message): unit
+// c = all the sets of chunk c, paired once as e(sum r_i pk_i, H(root)); rep = the set that
+// computed the root's H (plan_msg_dedup's first set of the root; without dedup the job's
+// own first set)
+static void units_same_message(const BatchPlan& plan, const std::vector<uint32_t>& msg_rep, uint32_t n, UnitPlan& u) {
+  const uint32_t C = (uint32_t)plan.chunk_off.size() - 1;
+  u.set_unit.assign(n, UNIT_NONE);
+  u.unit_off.resize(C + 1);
+  u.unit_rep.resize(C);
+  u.goff = plan.chunk_off;
+  u.members = plan.chunk_reqs;  // (every request is one set: request index == set index)
+  for (uint32_t c = 0; c < C; ++c) {
+    u.unit_off[c] = c;
+    const uint32_t first = plan.chunk_reqs[plan.chunk_off[c]];
+    u.unit_rep[c] = msg_rep.empty() ? first : msg_rep[first];
+    for (uint32_t k = plan.chunk_off[c]; k < plan.chunk_off[c + 1]; ++k) u.set_unit[plan.chunk_reqs[k]] = c;
+  }
+  u.unit_off[C] = C;
+  u.n_units = C;
+}
+
 struct InFlight {
   uint64_t n;
   explicit InFlight(uint64_t k) : n(k) { g_sets_in_flight.fetch_add(n, std::memory_order_relaxed); }
@@ -1211,18 +1235,19 @@ static hipError_t pass_wait(bls_gpu_ctx* ctx, hipStream_t s) {
 
 static int verify_body(bls_gpu_ctx* ctx, const bls_batch* in, int32_t* verdicts, bls_stats* stats,
                        uint32_t scalar_base, uint8_t* partial_out, int32_t* partial_status, uint32_t* partial_err,
-                       const std::vector<uint32_t>* req_bounds);
+                       const std::vector<uint32_t>* req_bounds, const SameMsgPlan* sm);
 
 // One call under the context's lock.  A call that fails part-way may leave the MSM's
 // bucket counters / tickets (reset only by the kernels' last workgroups) mid-pass: they
 // are zeroed again before the context takes another call.
 static int verify_impl(bls_gpu_ctx* ctx, const bls_batch* in, int32_t* verdicts, bls_stats* stats,
                        uint32_t scalar_base, uint8_t* partial_out, int32_t* partial_status,
-                       uint32_t* partial_err = nullptr, const std::vector<uint32_t>* req_bounds = nullptr) {
+                       uint32_t* partial_err = nullptr, const std::vector<uint32_t>* req_bounds = nullptr,
+                       const SameMsgPlan* sm = nullptr) {
   CTX_LOCK(ctx);
   ctx->wait_block = wait_blocks(in->n_sets);
   const int rc = verify_body(ctx, in, verdicts, stats, scalar_base, partial_out, partial_status, partial_err,
-                             req_bounds);
+                             req_bounds, sm);
   if (rc < 0 && ctx->msm_state) {
     (void)hipStreamSynchronize(ctx->stream);
     (void)hipMemsetAsync(ctx->msm_state, 0, sizeof(uint32_t) * MSM_STATE_WORDS, ctx->stream);
@@ -1233,7 +1258,7 @@ static int verify_impl(bls_gpu_ctx* ctx, const bls_batch* in, int32_t* verdicts,
 
 static int verify_body(bls_gpu_ctx* ctx, const bls_batch* in, int32_t* verdicts, bls_stats* stats,
                        uint32_t scalar_base, uint8_t* partial_out, int32_t* partial_status, uint32_t* partial_err,
-                       const std::vector<uint32_t>* req_bounds) {
+                       const std::vector<uint32_t>* req_bounds, const SameMsgPlan* sm) {
   const bool partial = partial_out != nullptr;
   HIPC(ctx, hipSetDevice(ctx->device));
   const uint32_t n = in->n_sets, R = in->n_reqs;
@@ -1242,7 +1267,8 @@ static int verify_body(bls_gpu_ctx* ctx, const bls_batch* in, int32_t* verdicts,
   if (const int rc = check_batch(ctx, in, "batch")) return rc;
   const InFlight in_flight(n);
   BatchPlan plan;
-  if (req_bounds) plan_batch_msgs(in, *req_bounds, plan);
+  if (sm) plan = sm->plan;  // every job a caller-defined chunk (plan_same_message)
+  else if (req_bounds) plan_batch_msgs(in, *req_bounds, plan);
   else plan_batch(in, plan);
   std::vector<uint32_t> msg_uniq, msg_rep;
   const uint32_t n_uniq = (ctx->debug_flags & BLS_DEBUG_NO_MSG_DEDUP) ? n : plan_msg_dedup(in->messages, n, msg_uniq, msg_rep);
@@ -1255,35 +1281,44 @@ static int verify_body(bls_gpu_ctx* ctx, const bls_batch* in, int32_t* verdicts,
   // verdicts and stats stay those of the chunked worker (worker.ts:56-88).
   const bool merged_eligible = !partial && plan.chunk_off.size() > 2 && plan.nonbatch_reqs.empty() && n > 0 &&
                                !(ctx->debug_flags & BLS_DEBUG_NO_MERGED_CHECK);
-  const bool merged_skipped = merged_eligible && ctx->last_merged_failed && merged_skip_after_fail() &&
+  // (same-message calls neither read nor write the context's merged-check history)
+  const bool merged_skipped = merged_eligible && !sm && ctx->last_merged_failed && merged_skip_after_fail() &&
                               !(ctx->debug_flags & BLS_DEBUG_MERGED_EVERY_PASS);
   const bool merged = merged_eligible && !merged_skipped;
   const uint32_t n_chunks = (uint32_t)plan.chunk_off.size() - 1;
   const uint32_t n_pk_idx = in->set_pk_offsets ? in->set_pk_offsets[n] : 0;
   // aggregated-signature path: virtual sets n + chunk and n + n_chunks + individual
   // request; the chunk groups' sum plan is staged with the inputs
-  const bool sigagg = n > 0 && use_sigagg(ctx, n);
+  // (a same-message call always: the per-set k_pset path would bring back one Miller
+  // loop pair per set)
+  const bool sigagg = n > 0 && (sm || use_sigagg(ctx, n));
   GsumPlan chunk_gsum, unit_gsum;
   UnitPlan units;
-  const bool use_units = sigagg && dedup && !(ctx->debug_flags & BLS_DEBUG_NO_UNITS) &&
-                         plan_units(in, plan, msg_rep, n, units);
+  // same-message jobs: one unit per job (chunk) holding all its sets, whatever the flags
+  if (sm && n_chunks > 0) units_same_message(plan, msg_rep, n, units);
+  const bool use_units = sm ? n_chunks > 0
+                            : sigagg && dedup && !(ctx->debug_flags & BLS_DEBUG_NO_UNITS) &&
+                                  plan_units(in, plan, msg_rep, n, units);
+  // ... and their sums of r_i pk_i and r_i sig_i by k_smsum, one wavefront per job
+  const bool smsum = sm && use_units;
   const uint32_t n_units = use_units ? units.n_units : 0;
   // f / chain layout: sets [0, n) | chunk signature sums [n, n + C) | units
   // [n + C, n + C + U) | individual requests' signature sums [n + C + U, .. + R)
   const uint32_t unit_base = n + n_chunks, indiv_vbase = n + n_chunks + n_units;
   const uint32_t n_total = sigagg ? indiv_vbase + R : n;
-  if (sigagg) {
+  if (sigagg && !smsum) {
     std::vector<uint32_t> goff(plan.chunk_off.begin(), plan.chunk_off.end());
     plan_gsum(in, goff, plan.chunk_reqs, chunk_gsum);
   }
-  if (use_units) plan_gsum_sets(units.goff, units.members, unit_gsum);
+  if (use_units && !smsum) plan_gsum_sets(units.goff, units.members, unit_gsum);
   // Merged signature sum: under the merged check the chunks' signature sums only ever
   // meet in the product of every f, and prod_c e(-g1, S_c) = e(-g1, sum_c S_c) after the
   // final exponentiation, so the first pass sums every chunk's r_i sig_i into ONE point
   // (chunk group 0; the other chunk groups are empty, so k_vset gives them f = 1) and
   // pairs it once.  A failing merged check re-sums per chunk and pairs each sum before
   // the per-chunk final exponentiations (k_chunk_coop), so chunk verdicts are unchanged.
-  const bool use_total = sigagg && merged && n_chunks > 1 && sig_total_on();
+  // (not for same-message jobs: each job's sum is paired in the first pass's launch)
+  const bool use_total = sigagg && !sm && merged && n_chunks > 1 && sig_total_on();
   // ... and under it the sum is one Pippenger MSM over the live sets (kernels/k_msm.hip)
   // instead of per-set [r] sig chains + k_gsum levels; the per-set RS are made (k_chain
   // role 2 alone) only when the merged check fails and the chunks' own sums are needed
@@ -1400,8 +1435,8 @@ static int verify_body(bls_gpu_ctx* ctx, const bls_batch* in, int32_t* verdicts,
       b.set_unit = c.take<uint32_t>(n);
       unit_rep_dev = c.take<uint32_t>(n_units);
       b.unit_off = c.take<uint32_t>(n_chunks + 1);
-      ugsets_dev = c.take<uint32_t>(units.members.size());
-      useg_dev = c.take<uint32_t>(unit_gsum.seg.size());
+      ugsets_dev = smsum ? nullptr : c.take<uint32_t>(units.members.size());
+      useg_dev = smsum ? nullptr : c.take<uint32_t>(unit_gsum.seg.size());
     }
     input_end = c.off;
     b.sig = c.take<G2A>(n);
@@ -1418,8 +1453,8 @@ static int verify_body(bls_gpu_ctx* ctx, const bls_batch* in, int32_t* verdicts,
     b.rpts = sigagg ? nullptr : c.take<G1J>(2ull * n);
     gtmp[0] = sigagg ? c.take<G2J>(gtmp_cap) : nullptr;
     gtmp[1] = sigagg ? c.take<G2J>(gtmp_cap) : nullptr;
-    utmp[0] = use_units ? c.take<G1J>(unit_gsum.level_off[1] + 1) : nullptr;
-    utmp[1] = use_units ? c.take<G1J>(unit_gsum.level_off[1] + 1) : nullptr;
+    utmp[0] = use_units && !smsum ? c.take<G1J>(unit_gsum.level_off[1] + 1) : nullptr;
+    utmp[1] = use_units && !smsum ? c.take<G1J>(unit_gsum.level_off[1] + 1) : nullptr;
     b.set_flag = c.take<uint32_t>(n);
     b.flag_count = c.take<uint32_t>(1);
     b.f = c.take<Fp12>(n_total);
@@ -1488,8 +1523,10 @@ static int verify_body(bls_gpu_ctx* ctx, const bls_batch* in, int32_t* verdicts,
     stage_copy(ctx, b.set_unit, units.set_unit.data(), sizeof(uint32_t) * n);
     stage_copy(ctx, unit_rep_dev, units.unit_rep.data(), sizeof(uint32_t) * n_units);
     stage_copy(ctx, b.unit_off, units.unit_off.data(), sizeof(uint32_t) * (n_chunks + 1));
-    stage_copy(ctx, ugsets_dev, units.members.data(), sizeof(uint32_t) * units.members.size());
-    stage_copy(ctx, useg_dev, unit_gsum.seg.data(), sizeof(uint32_t) * unit_gsum.seg.size());
+    if (!smsum) {
+      stage_copy(ctx, ugsets_dev, units.members.data(), sizeof(uint32_t) * units.members.size());
+      stage_copy(ctx, useg_dev, unit_gsum.seg.data(), sizeof(uint32_t) * unit_gsum.seg.size());
+    }
   }
   if (ml_shared) stage_copy(ctx, b.ml_dom, ml_dom.data(), sizeof(uint32_t) * ml_dom.size());
   if (sigagg) {
@@ -1544,7 +1581,10 @@ static int verify_body(bls_gpu_ctx* ctx, const bls_batch* in, int32_t* verdicts,
       // Miller loop (sets and virtual sets) in one launch
       HIPC(ctx, launch_k_chain(b, s, use_msm ? 0xBu : 0xFu)); dbg_sync(s, "k_chain");
       HIPC(ctx, hipEventRecord(ctx->ev[3], s));
-      if (use_msm) {
+      if (smsum) {
+        // each job's two pairing inputs in one step (kernels/k_smsg.hip)
+        HIPC(ctx, launch_k_smsum(b, unit_rep_dev, s)); dbg_sync(s, "k_smsum");
+      } else if (use_msm) {
         msm.cnt = ctx->msm_state;
         msm.ticket = ctx->msm_state + MSM_BUCKETS;
         HIPC(ctx, launch_k_msm(b, msm, n_chunks, n, s)); dbg_sync(s, "k_msm");
@@ -1552,7 +1592,7 @@ static int verify_body(bls_gpu_ctx* ctx, const bls_batch* in, int32_t* verdicts,
                              gtmp, n, s)) {
         return -1;
       }
-      if (use_units) {
+      if (use_units && !smsum) {
         // sum r_i pk_i per unit (levels over the members), then the units' chain entries
         b.gsets = ugsets_dev;
         const G1J* uin = nullptr;
@@ -1569,7 +1609,22 @@ static int verify_body(bls_gpu_ctx* ctx, const bls_batch* in, int32_t* verdicts,
       // the f-side shape is chosen once per call (other contexts change the sets in flight
       // meanwhile): the first pass's Miller-loop launch and stats->pass_shape use it
       if (!b.mlf_pl && k_mln_list_ok(b)) b.mlf_pl = mlf_per_lane();
-      HIPC(ctx, launch_k_mln(b, ctx->coop, 0, indiv_vbase, s)); dbg_sync(s, "k_mln");
+      // a same-message call's first pass has two Miller loops per job (its unit and its
+      // signature sum) and one per 1-set job: few items that never share f, so they run as
+      // the cooperative single-pair loops, one wavefront each (launch_k_mln_coop: ~1 ms
+      // where the SIMT pair takes ~7 ms), while they fit coop_ml_max()
+      hipError_t ml_rc = hipErrorNotSupported;
+      if (sm && k_mln_list_ok(b) && !(ctx->debug_flags & BLS_DEBUG_MLF_PL_MASK)) {
+        std::vector<uint32_t> items(plan.nonbatch_reqs);
+        for (uint32_t ch = 0; ch < n_chunks; ++ch) items.push_back(n + ch);
+        for (uint32_t u = 0; u < n_units; ++u) items.push_back(unit_base + u);
+        if (items.size() <= coop_ml_max()) {
+          stage_copy(ctx, own_sets_dev, items.data(), sizeof(uint32_t) * items.size());
+          ml_rc = launch_k_mln_coop(b, ctx->coop, 0, (uint32_t)items.size(), own_sets_dev, s);
+        }
+      }
+      if (ml_rc == hipErrorNotSupported) ml_rc = launch_k_mln(b, ctx->coop, 0, indiv_vbase, s);
+      HIPC(ctx, ml_rc); dbg_sync(s, "k_mln");
     } else {
       HIPC(ctx, launch_k_pset(b, ctx->coop, s)); dbg_sync(s, "k_pset");
       HIPC(ctx, hipEventRecord(ctx->ev[3], s));
@@ -1654,7 +1709,7 @@ static int verify_body(bls_gpu_ctx* ctx, const bls_batch* in, int32_t* verdicts,
   bool merged_pass = merged && merged_verdict == 1;
   bool chunk_fe_kept = false;
   for (uint32_t r = 0; merged_pass && r < R; ++r) merged_pass = merged_status[r] == BLS_OK;
-  if (merged) ctx->last_merged_failed = !merged_pass;
+  if (merged && !sm) ctx->last_merged_failed = !merged_pass;
   if (merged_pass) {
     for (uint32_t ch = 0; ch < n_chunks; ++ch) chunk_ok[ch] = 1;
   } else if (n_chunks > 0 && !partial) {
@@ -2018,6 +2073,42 @@ int bls_gpu_verify_many(bls_gpu_ctx* ctx, const bls_batch* batches, uint32_t n_b
   all.signature_lens = lens ? sig_lens.data() : nullptr;
   all.seed = batches[0].seed;  // scalars: one random batch per pass (verdicts do not depend on them)
   return verify_impl(ctx, &all, verdicts, stats, 0u, nullptr, nullptr, nullptr, &req_bounds);
+}
+
+int bls_gpu_verify_same_message(bls_gpu_ctx* ctx, const bls_same_msg_batch* in, int32_t* set_verdicts,
+                                bls_stats* stats) {
+  if (!ctx || !in) return -2;
+  if (stats) memset(stats, 0, sizeof(*stats));
+  if (in->n_jobs == 0) return 0;
+  const uint32_t n = in->n_sets, J = in->n_jobs;
+  auto bad = [&](const char* what) {
+    CTX_LOCK(ctx);
+    snprintf(ctx->err, sizeof(ctx->err), "same-message batch: %s", what);
+    return -2;
+  };
+  if (const char* what = check_same_message(in, set_verdicts)) return bad(what);
+  // the call as n one-set batchable requests over table indices, the job's root per set
+  std::vector<uint32_t> off(n + 1);
+  for (uint32_t i = 0; i <= n; ++i) off[i] = i;
+  std::vector<uint8_t> batchable(n, 1), msgs(32ull * n);
+  for (uint32_t j = 0; j < J; ++j)
+    for (uint32_t i = in->job_set_offsets[j]; i < in->job_set_offsets[j + 1]; ++i)
+      memcpy(&msgs[32ull * i], in->messages + 32ull * j, 32);
+  SameMsgPlan sm;
+  plan_same_message(in, sm);
+  for (uint32_t r : sm.plan.nonbatch_reqs) batchable[r] = 0;
+  bls_batch all;
+  memset(&all, 0, sizeof(all));
+  all.n_sets = n;
+  all.n_reqs = n;
+  all.req_set_offsets = off.data();
+  all.req_batchable = batchable.data();
+  all.set_pk_offsets = off.data();
+  all.pk_indices = in->pk_indices;
+  all.messages = msgs.data();
+  all.signatures = in->signatures;
+  all.seed = in->seed;
+  return verify_impl(ctx, &all, set_verdicts, stats, 0u, nullptr, nullptr, nullptr, nullptr, &sm);
 }
 
 int bls_gpu_partial(bls_gpu_ctx* ctx, const bls_batch* in, uint32_t set_index_base, uint8_t* out576,

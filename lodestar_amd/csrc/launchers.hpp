@@ -57,6 +57,9 @@ hipError_t launch_k_vset(const bls::PipeBufs& b, const bls::G2J* sums, uint32_t 
 hipError_t launch_k_gsum1(const bls::PipeBufs& b, const uint32_t* seg, uint32_t n_seg, const bls::G1J* in,
                           bls::G1J* out, hipStream_t s);
 hipError_t launch_k_uset(const bls::PipeBufs& b, const bls::G1J* sums, const uint32_t* unit_rep, hipStream_t s);
+// same-message jobs (kernels/k_smsg.hip): chunk c's sum r_i pk_i -> unit b.unit_base + c and
+// sum r_i sig_i -> virtual set b.n_sets + c, one wavefront per chunk (one unit per chunk)
+hipError_t launch_k_smsum(const bls::PipeBufs& b, const uint32_t* unit_rep, hipStream_t s);
 #define GSUM_FAN 4u  // points per k_gsum segment (a 16-set chunk: two levels of 3 additions)
 hipError_t launch_k_hash_to_g2(const uint8_t* msgs, uint32_t n, uint8_t* out192, hipStream_t s);
 hipError_t launch_k_sig_aggregate(const uint8_t* in96, uint32_t n, const uint32_t* off, uint32_t n_lists,

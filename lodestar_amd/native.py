@@ -12,7 +12,7 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from ._abi import ERR_ADMISSION, BlsAdmission, BlsBatch, BlsStats, load_library
+from ._abi import ERR_ADMISSION, BlsAdmission, BlsBatch, BlsSameMsgBatch, BlsStats, load_library
 
 
 def _ptr(a: np.ndarray | None):
@@ -167,6 +167,51 @@ def pack_requests(requests, seed: bytes | None = None) -> PackedBatch:
     return pb
 
 
+@dataclass
+class PackedSameMsg:
+    """SoA form of one bls_gpu_verify_same_message call (bls_same_msg_batch)."""
+
+    job_set_offsets: np.ndarray  # uint32[n_jobs + 1]
+    messages: np.ndarray  # uint8[n_jobs * 32]
+    pk_indices: np.ndarray  # uint32[n_sets]
+    signatures: np.ndarray  # uint8[n_sets * 96]
+    seed: bytes | None = None
+
+    @property
+    def n_jobs(self) -> int:
+        return len(self.job_set_offsets) - 1
+
+    @property
+    def n_sets(self) -> int:
+        return int(self.job_set_offsets[-1])
+
+
+def pack_same_message(jobs, seed: bytes | None = None) -> PackedSameMsg:
+    """jobs: list of (message32, [table index...], [sig96...]), one signing root per job
+    and one (index, signature) pair per set."""
+    offs, msgs, idx, sigs = [0], [], [], []
+    for msg, indices, job_sigs in jobs:
+        if len(msg) != 32:
+            raise ValueError("signing roots are 32 bytes")
+        if len(indices) != len(job_sigs):
+            raise ValueError("a same-message job carries one signature per key index")
+        msgs.append(bytes(msg))
+        idx.extend(int(i) for i in indices)
+        for sig in job_sigs:
+            sb = bytes(sig)
+            if len(sb) != 96:
+                raise ValueError("signatures are 96 bytes (compressed G2)")
+            sigs.append(sb)
+        offs.append(len(idx))
+    return PackedSameMsg(
+        job_set_offsets=np.array(offs, dtype=np.uint32),
+        messages=np.frombuffer(b"".join(msgs), dtype=np.uint8).copy() if msgs else np.zeros(32, np.uint8),
+        pk_indices=np.array(idx if idx else [0], dtype=np.uint32),
+        signatures=np.frombuffer(b"".join(sigs), dtype=np.uint8).copy() if sigs else np.zeros(96, np.uint8),
+        seed=seed,
+    )
+
+
 class GpuContext:
     def __init__(self, device: int = 0, high_priority: bool = False):
         """high_priority: the context's stream outranks normal contexts' queued kernels
@@ -270,6 +315,34 @@ class GpuContext:
             out.append(verdicts[off: off + pb.n_reqs])
             off += pb.n_reqs
         return out, stats
+
+    def verify_same_message_packed(self, ps: PackedSameMsg) -> tuple[int, np.ndarray, BlsStats]:
+        """bls_gpu_verify_same_message as it is: (return code, n_sets verdicts, stats)."""
+        b = BlsSameMsgBatch()
+        b.n_jobs, b.n_sets = ps.n_jobs, ps.n_sets
+        keep = [np.ascontiguousarray(getattr(ps, f)) for f in ("job_set_offsets", "messages", "pk_indices",
+                                                                "signatures")]
+        b.job_set_offsets, b.messages, b.pk_indices, b.signatures = (_ptr(a) for a in keep)
+        seed_buf = None
+        if ps.seed is not None:
+            seed_buf = ctypes.create_string_buffer(bytes(ps.seed), 32)
+            b.seed = ctypes.cast(seed_buf, ctypes.c_void_p)
+        verdicts = np.zeros(max(ps.n_sets, 1), dtype=np.int32)
+        stats = BlsStats()
+        rc = self.lib.bls_gpu_verify_same_message(self._h, ctypes.byref(b), _ptr(verdicts), ctypes.byref(stats))
+        return rc, verdicts[: ps.n_sets], stats
+
+    def verify_same_message(self, jobs, seed: bytes | None = None) -> tuple[list[np.ndarray], BlsStats]:
+        """verifySignatureSetsSameMessage for several jobs in one native call
+        (bls_gpu_verify_same_message).  jobs: list of (message32, [table index...],
+        [sig96...]); each job is ONE random-scalar batch over its sets.  Returns one int32
+        array per job -- per set 1 valid, 0 invalid, -code an error under the one-set rules
+        (all 1 when the job's batch passes) -- and the call's stats."""
+        ps = jobs if isinstance(jobs, PackedSameMsg) else pack_same_message(jobs, seed)
+        rc, verdicts, stats = self.verify_same_message_packed(ps)
+        self._check(rc, "bls_gpu_verify_same_message")
+        off = ps.job_set_offsets
+        return [verdicts[int(off[j]): int(off[j + 1])] for j in range(ps.n_jobs)], stats
 
     def partial(self, pb: PackedBatch, set_index_base: int):
         """Miller-loop partial of this shard of a sharded call (bls_gpu_partial):

@@ -31,6 +31,16 @@ with GPU contexts in place of worker threads:
 * metrics: `metrics.bls.aggregatedPubkeys` and the `metrics.blsThreadPool.*` series
   under the reference's names (lodestar_amd/metrics.py, lodestar.ts:378-446).
 * `close()` (index.ts:176-197) rejects pending jobs with QUEUE_ABORTED.
+* `verify_signature_sets_same_message(sets, message)` (IBlsVerifier
+  .verifySignatureSetsSameMessage -> boolean[]; unaggregated gossip attestations): the
+  sets of one call all sign `message`.  It is queued as its own job kind; an idle
+  context takes every same-message job that is ready, up to `max_sets_per_call` sets, in
+  ONE bls_gpu_verify_same_message call, where each job is one random-scalar batch over
+  all its sets (the reference's aggregateWithRandomness: two Miller loops and one final
+  exponentiation per job) and a failing job's sets are verified on their own.  A set's
+  verdict is True iff its code is 1 (an error code is False, as the reference maps a
+  throwing set).  Sets whose key is not a table index (raw bytes, an index list) do not
+  enter the batch: each goes through the existing path as a one-set batchable request.
 
 * several devices (`devices=[0, 1, ...]`, one verifier per node): the reference's pool
   spreads one call's 128-set jobs over every worker of the process (index.ts:153-166,
@@ -115,6 +125,17 @@ class _Job:
     added: float
 
 
+@dataclass
+class _SameMsgJob:
+    """One verifySignatureSetsSameMessage call's table-index sets (its own job kind)."""
+
+    message: bytes
+    indices: list
+    sigs: list
+    future: Future
+    added: float
+
+
 def set_weight(pk) -> float:
     """Routing weight of one set: 1 for a single key, 1 + k / AGG_KEY_WEIGHT for an
     aggregate of k table keys (a G1 addition is ~11 of a set's ~12.7k Fp products, so
@@ -180,6 +201,7 @@ class GpuBlsVerifier:
             self.load_pubkeys(pubkeys48)
         self._cv = threading.Condition()
         self._jobs: list[_Job] = []
+        self._sm_jobs: list[_SameMsgJob] = []
         self._buffer: list[_Job] = []
         self._buffer_sigs = 0
         self._buffer_first = 0.0
@@ -244,6 +266,80 @@ class GpuBlsVerifier:
                 and sum(self._slot_ctxs) > 0 and all(self._slot_ctxs)):
             return self._split_call(sets)
         return self._queue_call(sets, batchable)
+
+    def verify_signature_sets_same_message(self, sets, message: bytes) -> list[bool]:
+        return self.verify_signature_sets_same_message_async(sets, message).result()
+
+    def verify_signature_sets_same_message_async(self, sets, message: bytes) -> Future:
+        """IBlsVerifier.verifySignatureSetsSameMessage: `sets` are (pubkey, signature) pairs
+        (or objects with .pubkey / .signature) that all sign `message`; the future resolves
+        to one bool per set, True iff the set is valid.  Table-index keys form one
+        same-message job (one random-scalar batch over all of them; module doc); a set
+        whose key is raw bytes or an index list is verified through the existing path as a
+        one-set batchable request."""
+        pairs = [(s.pubkey, s.signature) if hasattr(s, "pubkey") else (s[0], s[1]) for s in sets]
+        message = bytes(message)
+        if len(message) != 32:
+            raise ValueError("signing roots are 32 bytes")
+        out: Future = Future()
+        n = len(pairs)
+        if n == 0:
+            out.set_result([])
+            return out
+        if not self._ctxs and self.init_errors:
+            raise self.init_errors[0]
+        results: list = [None] * n
+        lock = threading.Lock()
+        pending = [0]
+
+        def part_done(positions, f, single):
+            with lock:
+                if out.done():
+                    return
+                if f.exception() is not None and not isinstance(f.exception(), BlsError):
+                    out.set_exception(f.exception())
+                    return
+                if single:  # a one-set request of the existing path: an erroring set is False
+                    results[positions[0]] = f.exception() is None and f.result() is True
+                else:
+                    for p, code in zip(positions, f.result()):
+                        results[p] = int(code) == 1
+                pending[0] -= 1
+                if pending[0] == 0:
+                    out.set_result(results)
+
+        # an int that is no uint32 can index no table: False, without a GPU call
+        no_index = {k for k, (pk, _) in enumerate(pairs) if isinstance(pk, int) and not 0 <= pk < 1 << 32}
+        for k in no_index:
+            results[k] = False
+        in_job = [k for k, (pk, sig) in enumerate(pairs)
+                  if isinstance(pk, int) and k not in no_index and len(bytes(sig)) == 96]
+        batched = set(in_job) | no_index
+        others = [k for k in range(n) if k not in batched]
+        if not in_job and not others:
+            out.set_result(results)
+            return out
+        parts = []
+        if in_job:
+            job = _SameMsgJob(message, [pairs[k][0] for k in in_job], [bytes(pairs[k][1]) for k in in_job], Future(),
+                              time.monotonic())
+            parts.append((in_job, job.future, False))
+        else:
+            job = None
+        pending[0] = len(parts) + len(others)
+        if job is not None:
+            with self._cv:
+                if self._closed:
+                    job.future.set_exception(QueueAborted("QUEUE_ABORTED"))
+                else:
+                    self._sm_jobs.append(job)
+                    self._cv.notify_all()
+        for k in others:
+            j = self._queue([SignatureSet(pairs[k][0], message, pairs[k][1])], True)
+            parts.append(([k], j.future, True))
+        for positions, f, single in parts:
+            f.add_done_callback(lambda f, positions=positions, single=single: part_done(positions, f, single))
+        return out
 
     def _queue_call(self, sets: list, batchable: bool) -> Future:
         """The reference's path: chunkifyMaximizeChunkSize(sets, 128) jobs, AND-ed."""
@@ -338,9 +434,9 @@ class GpuBlsVerifier:
     def close(self) -> None:
         with self._cv:
             self._closed = True
-            pending = self._jobs + self._buffer
+            pending = self._jobs + self._buffer + self._sm_jobs
             pinned = [p for lst in self._pinned for p in lst]
-            self._jobs, self._buffer = [], []
+            self._jobs, self._buffer, self._sm_jobs = [], [], []
             self._pinned = [[] for _ in self._pinned]
             self._cv.notify_all()
         for j in pending:
@@ -461,6 +557,15 @@ class GpuBlsVerifier:
             total += len(j.sets)
         return jobs
 
+    def _prepare_same_message_work(self) -> list:
+        """every same-message job that is ready, up to max_sets_per_call sets"""
+        jobs, total = [], 0
+        while self._sm_jobs and total < self.max_sets_per_call:
+            j = self._sm_jobs.pop(0)
+            jobs.append(j)
+            total += len(j.indices)
+        return jobs
+
     def _my_turn(self, slot: int) -> bool:
         """Least-loaded routing: the slot takes queued jobs only while no other slot with
         an idle context carries less outstanding set weight (ties: the lower slot)."""
@@ -477,7 +582,7 @@ class GpuBlsVerifier:
     def _worker(self, ctx, slot: int, wid: int):
         tp = self.metrics.blsThreadPool
         while True:
-            pin, jobs = None, None
+            pin, jobs, sm_jobs = None, None, None
             with self._cv:
                 self._idle[slot] += 1
                 while True:
@@ -487,22 +592,31 @@ class GpuBlsVerifier:
                     if self._pinned[slot]:
                         pin = self._pinned[slot].pop(0)
                         break
+                    if self._sm_jobs and self._my_turn(slot):
+                        sm_jobs = self._prepare_same_message_work()
+                        if sm_jobs:
+                            break
                     if self._jobs and self._my_turn(slot):
                         jobs = self._prepare_work()
                         if jobs:
                             break
                     self._cv.wait(timeout=0.05)
                 self._idle[slot] -= 1
-                sets = pin.sets if pin is not None else [s for j in jobs for s in j.sets]
-                weight = sum(set_weight(pk) for pk, _, _ in sets)
+                if sm_jobs is not None:
+                    keys = [i for j in sm_jobs for i in j.indices]
+                else:
+                    keys = [pk for pk, _, _ in (pin.sets if pin is not None else [s for j in jobs for s in j.sets])]
+                weight = sum(set_weight(pk) for pk in keys)
                 self._load[slot] += weight
                 st = self.slot_stats[slot]
                 st["calls"] += 1
-                st["sets"] += len(sets)
+                st["sets"] += len(keys)
                 st["weight"] += weight
             try:
                 if pin is not None:
                     self._run_pinned(ctx, pin)
+                elif sm_jobs is not None:
+                    self._run_same_message_jobs(ctx, sm_jobs, wid, tp)
                 else:
                     self._run_jobs(ctx, jobs, wid, tp)
             finally:
@@ -517,6 +631,33 @@ class GpuBlsVerifier:
         except Exception as e:  # noqa: BLE001 - the call rejects with it
             res = e
         pin.done(res, ctx)
+
+    def _run_same_message_jobs(self, ctx, jobs, wid, tp):
+        """every job handed over in one bls_gpu_verify_same_message call; each job's future
+        resolves to its sets' codes (the caller maps them to bools)"""
+        now = time.monotonic()
+        n_sets = sum(len(j.indices) for j in jobs)
+        for j in jobs:
+            tp.jobWaitTime.observe(now - j.added)
+        tp.totalJobsGroupsStarted.inc(1)
+        tp.totalJobsStarted.inc(len(jobs))
+        tp.totalSigSetsStarted.inc(n_sets)
+        try:
+            t0 = time.perf_counter()
+            verdicts, stats = ctx.verify_same_message([(j.message, j.indices, j.sigs) for j in jobs])
+            t1 = time.perf_counter()
+        except Exception as e:  # noqa: BLE001 - reject every job of the call
+            for j in jobs:
+                j.future.set_exception(e)
+            tp.errorJobsSignatureSetsCount.inc(n_sets)
+            return
+        tp.jobsWorkerTime.inc({"workerId": wid}, stats.device_ms / 1e3)
+        tp.latencyFromWorker.observe(max(0.0, (t1 - t0) - stats.device_ms / 1e3))
+        tp.batchRetries.inc(stats.batch_retries)
+        tp.batchSigsSuccess.inc(stats.batch_sigs_success)
+        for j, v in zip(jobs, verdicts):
+            j.future.set_result([int(x) for x in v])
+            tp.successJobsSignatureSetsCount.inc(len(j.indices))
 
     def _run_jobs(self, ctx, jobs, wid, tp):
         if self.call_log is not None:
