@@ -248,6 +248,23 @@ def build_hostsim(verbose: bool = True) -> Path:
     return out
 
 
+def build_fp2_rows_host(verbose: bool = True) -> Path:
+    """CPU build of the row-wise lazy Fp2 product (tests/native/fp2_rows_host.cpp), for tests/."""
+    src = ROOT / "tests" / "native" / "fp2_rows_host.cpp"
+    out = ROOT / "tests" / "native" / "libfp2_rows_host.so"
+    key = hashlib.sha256(_headers_digest().encode() + src.read_bytes()).hexdigest()[:16]
+    stamp = out.with_suffix(".stamp")
+    if out.exists() and stamp.exists() and stamp.read_text() == key:
+        return out
+    cmd = ["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-I", str(CSRC), "-I", str(ROOT / "include"), "-o",
+           str(out), str(src)]
+    if verbose:
+        print("[build]", " ".join(cmd), flush=True)
+    subprocess.run(cmd, check=True)
+    stamp.write_text(key)
+    return out
+
+
 def build_smsum_host(verbose: bool = True, out: Path | None = None, extra: list[str] | None = None) -> Path:
     """CPU restatement of k_smsum and the same-message plan (tests/native/smsum_host.cpp), a
     stand-alone program for tests/; `extra` compiler flags (a sanitizer build) need their

@@ -13,6 +13,8 @@
 #include "../launchers.hpp"
 #include "../bls/selftest_ops.hpp"
 
+static_assert(BLS_BLOCK == 64, "one wavefront per block (the Fp2 primitive's LDS slot, FOP_FP2_*_W)");
+
 namespace bls {
 
 // op ids of bls_gpu_field_op_test (include/lodestar_bls.h; BLS_FIELD_OP_D28 selects the TU)
@@ -46,6 +48,9 @@ enum : uint32_t {
   FOP_FP2_INV,
   FOP_FP2_SQRT,
   FOP_LIN8,
+  FOP_FP2_MUL_W,    // fp2_mul_prim: the out-of-line lazy Fp2 product, LDS slot included
+  FOP_FP2_SQR_W,    // fp2_sqr_prim
+  FOP_FP2_CHAIN_W,  // four dependent products through the same slot
   FOP_COUNT
 };
 #define FOP_D28_FLAG 0x100u
@@ -57,7 +62,9 @@ constexpr int field_op_in_words(uint32_t op) {
                  op == FOP_CANON3 || op == FOP_SQR || op == FOP_SQR_D28_LAZY || op == FOP_INV ||
                  op == FOP_INV_GCD || op == FOP_SQRT
              ? 12
-         : op == FOP_FP2_MUL_D28 || op == FOP_FP2_MUL || op == FOP_FP2_MUL_S || op == FOP_LZ_FP2_OPS ? 48
+         : op == FOP_FP2_MUL_D28 || op == FOP_FP2_MUL || op == FOP_FP2_MUL_S || op == FOP_LZ_FP2_OPS ||
+                 op == FOP_FP2_MUL_W || op == FOP_FP2_CHAIN_W
+             ? 48
          : op == FOP_LZ_MUL_RAW                                                                        ? 28
          : op == FOP_LZ_SQR_RAW                                                                        ? 14
          : op == FOP_LIN8                                                                              ? FOP_LIN8_IN
@@ -65,7 +72,8 @@ constexpr int field_op_in_words(uint32_t op) {
 }
 constexpr int field_op_out_words(uint32_t op) {
   return op == FOP_FP2_MUL_D28 || op == FOP_FP2_SQR_D28 || op == FOP_FP2_MUL || op == FOP_FP2_SQR ||
-                 op == FOP_FP2_MUL_S || op == FOP_FP2_INV
+                 op == FOP_FP2_MUL_S || op == FOP_FP2_INV || op == FOP_FP2_MUL_W || op == FOP_FP2_SQR_W ||
+                 op == FOP_FP2_CHAIN_W
              ? 24
          : op == FOP_LZ_MUL_RAW || op == FOP_LZ_SQR_RAW ? 14
          : op == FOP_LZ_FP_OPS                          ? 120
@@ -153,6 +161,18 @@ __device__ __forceinline__ void field_op_body(const uint32_t* x, uint32_t* y) {
     y[0] = fp2_sqrt(fop_ld2(x, 0), r) ? 1u : 0u;
     fop_st2(y + 1, 0, r);
   }
+#if defined(__HIP_DEVICE_COMPILE__)  // the out-of-line primitives exist on the device only
+  else if constexpr (OP == FOP_FP2_MUL_W) fop_st2(y, 0, fp2_mul_prim(fop_ld2(x, 0), fop_ld2(x, 1)));
+  else if constexpr (OP == FOP_FP2_SQR_W) fop_st2(y, 0, fp2_sqr_prim(fop_ld2(x, 0)));
+  else if constexpr (OP == FOP_FP2_CHAIN_W) {
+    // a b, (a b) b, b (a b^2), (a b^3)(a b) = a^2 b^4: the slot takes b, b, a b^2, a b in turn
+    const Fp2 a = fop_ld2(x, 0), b = fop_ld2(x, 1);
+    const Fp2 r1 = fp2_mul_prim(a, b);
+    const Fp2 r2 = fp2_mul_prim(r1, b);
+    const Fp2 r3 = fp2_mul_prim(b, r2);
+    fop_st2(y, 0, fp2_mul_prim(r3, r1));
+  }
+#endif
 #endif
 }
 
@@ -255,6 +275,9 @@ static hipError_t field_op_launch(uint32_t op, const uint32_t* in, uint32_t n, u
     FOP_CASE(FOP_SQRT);
     FOP_CASE(FOP_FP2_INV);
     FOP_CASE(FOP_FP2_SQRT);
+    FOP_CASE(FOP_FP2_MUL_W);
+    FOP_CASE(FOP_FP2_SQR_W);
+    FOP_CASE(FOP_FP2_CHAIN_W);
     case FOP_LIN8:
       k_field_lin8<true><<<bls_grid_for(n), BLS_BLOCK, 0, s>>>(in, n, out);
       break;

@@ -29,10 +29,16 @@
 // chains the kernel needs 4,544 B of scratch per lane, a reservation of 568 MiB per
 // queue that took the runtime past its scratch grant with the bench's queues (DESIGN.md
 // §3, profiles/r03_chain_inl28_resources.txt) -- the round-2 "never finished".
+// The G2 roles' Fp2 products and squares are the out-of-line lazy primitives
+// (BLS_FP2_PRIM: field.hpp fp2_mul_w / fp2_sqr_w; 2,288 B of scratch per lane against
+// 2,576 B with three Fp products per Fp2 product, and a 6 KB LDS slot per block).
 #define BLS_FP_D28 1
+#define BLS_FP2_PRIM 1
 #include "../launchers.hpp"
 
 using namespace bls;
+
+static_assert(BLS_BLOCK == BLS_FP2_SLOT_LANES, "the Fp2 primitive's LDS slot holds one wavefront per block");
 
 namespace {
 

@@ -18,13 +18,23 @@
 // products per pair with T, P and Q only; the f side 62 squarings (36) per two pairs
 // plus 68 sparse line products (39) per pair -> ~5,700 products per pair, each kernel
 // with half the live state.
+//
+// The Fp2 products and squares of both sides are the out-of-line lazy primitives
+// (BLS_FP2_PRIM: field.hpp fp2_mul_w / fp2_sqr_w, one call and one reduction per
+// coefficient instead of three Fp products; the second operand of a product travels
+// through a lane-private LDS slot, 6 KB per block).  store_line's Fp2 x Fp keeps the two Fp
+// products: it has two reductions either way, and the Fp2 primitive would add 392
+// multiply-adds.
 #define BLS_FP_D28 1
+#define BLS_FP2_PRIM 1
 #include <stdlib.h>
 
 #include "../launchers.hpp"
 #include "bls/pairing.hpp"
 
 using namespace bls;
+
+static_assert(BLS_BLOCK == BLS_FP2_SLOT_LANES, "the Fp2 primitive's LDS slot holds one wavefront per block");
 
 namespace {
 
