@@ -364,7 +364,7 @@ int bls_gpu_kernel_probe(bls_gpu_ctx* ctx, const char* name, uint32_t lanes, uin
  * path (stage_exact_set) instead of the cooperative programs, so parity tests cover both. */
 #define BLS_DEBUG_FORCE_EXACT 1u
 /* Test / bench hook: compute hash_to_field + SSWU per set even when sets share a
- * signing root (the default dedups them, plan_msg_dedup in bls/pipeline.hpp). */
+ * signing root (the default dedups them, plan_msg_dedup in bls/plan.hpp). */
 #define BLS_DEBUG_NO_MSG_DEDUP 2u
 /* Test / bench hook: skip the merged check (one final exponentiation over every
  * chunk's sets before the per-chunk ones) and go straight to the chunk verdicts. */

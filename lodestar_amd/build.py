@@ -235,7 +235,8 @@ def build_hostsim(verbose: bool = True) -> Path:
     src = ROOT / "tests" / "native" / "hostsim.cpp"
     out = ROOT / "tests" / "native" / "libhostsim.so"
     hdr = _headers_digest()
-    key = hashlib.sha256(hdr.encode() + src.read_bytes()).hexdigest()[:16]
+    own = b"".join(p.read_bytes() for p in sorted(src.parent.glob("*.hpp")))  # what it includes from beside it
+    key = hashlib.sha256(hdr.encode() + src.read_bytes() + own).hexdigest()[:16]
     stamp = out.with_suffix(".stamp")
     if out.exists() and stamp.exists() and stamp.read_text() == key:
         return out
@@ -265,13 +266,14 @@ def build_fp2_rows_host(verbose: bool = True) -> Path:
     return out
 
 
-def build_smsum_host(verbose: bool = True, out: Path | None = None, extra: list[str] | None = None) -> Path:
-    """CPU restatement of k_smsum and the same-message plan (tests/native/smsum_host.cpp), a
-    stand-alone program for tests/; `extra` compiler flags (a sanitizer build) need their
-    own `out`."""
-    src = ROOT / "tests" / "native" / "smsum_host.cpp"
-    out = out or ROOT / "tests" / "native" / "smsum_host"
-    key = hashlib.sha256((_headers_digest() + " ".join(extra or [])).encode() + src.read_bytes()).hexdigest()[:16]
+def _build_host_program(name: str, deps: tuple[str, ...], verbose: bool, out: Path | None,
+                        extra: list[str] | None) -> Path:
+    """A stand-alone CPU test program tests/native/<name>.cpp (deps: further files beside it)."""
+    native = ROOT / "tests" / "native"
+    src = native / f"{name}.cpp"
+    out = out or native / name
+    key = hashlib.sha256((_headers_digest() + " ".join(extra or [])).encode() + src.read_bytes()
+                         + b"".join((native / d).read_bytes() for d in deps)).hexdigest()[:16]
     stamp = out.with_suffix(".stamp")
     if out.exists() and stamp.exists() and stamp.read_text() == key:
         return out
@@ -282,6 +284,19 @@ def build_smsum_host(verbose: bool = True, out: Path | None = None, extra: list[
     subprocess.run(cmd, check=True)
     stamp.write_text(key)
     return out
+
+
+def build_smsum_host(verbose: bool = True, out: Path | None = None, extra: list[str] | None = None) -> Path:
+    """CPU restatement of k_smsum and the same-message plan (tests/native/smsum_host.cpp), a
+    stand-alone program for tests/; `extra` compiler flags (a sanitizer build) need their
+    own `out`."""
+    return _build_host_program("smsum_host", (), verbose, out, extra)
+
+
+def build_plan_host(verbose: bool = True, out: Path | None = None, extra: list[str] | None = None) -> Path:
+    """The host-side planners of a verify pass (bls/plan.hpp) run over their edge shapes
+    (tests/native/plan_host.cpp), a stand-alone program for tests/; `extra` as above."""
+    return _build_host_program("plan_host", ("plan_exports.hpp",), verbose, out, extra)
 
 
 def build_cpu_baseline(verbose: bool = True) -> Path:
@@ -325,4 +340,5 @@ if __name__ == "__main__":
     build_napi()
     build_hostsim()
     build_smsum_host()
+    build_plan_host()
     build_cpu_baseline()

@@ -26,6 +26,7 @@
 #include "../../../include/lodestar_bls.h"
 #include "hash_to_curve.hpp"
 #include "pairing.hpp"
+#include "plan_shape.hpp"
 
 namespace bls {
 
@@ -35,7 +36,6 @@ namespace bls {
 // A group's virtual set (index n_sets + chunk, n_sets + n_chunks + individual
 // request) holds HQ = affine(sum of the group's RS) and RP = -g1.
 enum : int { CH_HQ = 0, CH_RP = 4, CH_RS = 7, CHAIN_WORDS = 13 };
-#define UNIT_NONE 0xFFFFFFFFu
 
 struct PipeBufs {
   uint32_t n_sets, n_reqs, n_chunks, n_indiv;
@@ -151,8 +151,6 @@ struct GroupBufs {
   // ref[g] = REF_CHUNK | c: compare with chunk c's checked value ref_fe[c] instead
   const Fp12* ref_fe;
 };
-#define REF_CHUNK 0x80000000u
-#define REF_NONE 0xFFFFFFFFu  // no comparison (the chunk indices stay far below 2^31 - 1)
 
 BLS_HD void scalar_words_from_be32(const uint8_t* b, uint32_t k[8]) {
   for (int i = 0; i < 8; ++i) {
@@ -468,151 +466,6 @@ BLS_HD void stage_indiv(const PipeBufs& b, uint32_t t) {
 
 }  // namespace bls
 
-// Host-side planning (plain host functions; parsed but not emitted in the device pass).
-#include <stdlib.h>
-#include <string.h>
-#include <vector>
-
-namespace bls {
-
-// chunkifyMaximizeChunkSize (beacon-node/src/chain/bls/multithread/utils.ts:4-19)
-static inline void chunkify_maximize_chunk_size(uint32_t n, uint32_t min_per_chunk, std::vector<uint32_t>& bounds) {
-  bounds.clear();
-  uint32_t chunk_count = n / min_per_chunk;
-  bounds.push_back(0);
-  if (chunk_count <= 1) {
-    bounds.push_back(n);
-    return;
-  }
-  uint32_t per = (n + chunk_count - 1) / chunk_count;
-  for (uint32_t i = per; i < n; i += per) bounds.push_back(i);
-  bounds.push_back(n);
-}
-
-// Host-side plan of one verify call: chunks over the batchable requests
-// (BATCHABLE_MIN_PER_CHUNK = 16, worker.ts:17,56) and the non-batchable list.
-struct BatchPlan {
-  std::vector<uint32_t> chunk_off, chunk_reqs, nonbatch_reqs;
-};
-
-static inline void plan_batch(const bls_batch* in, BatchPlan& p) {
-  std::vector<uint32_t> batchable;
-  p.nonbatch_reqs.clear();
-  for (uint32_t r = 0; r < in->n_reqs; ++r) {
-    if (in->req_batchable && in->req_batchable[r]) batchable.push_back(r);
-    else p.nonbatch_reqs.push_back(r);
-  }
-  p.chunk_off.clear();
-  p.chunk_reqs = batchable;
-  if (batchable.empty()) {
-    p.chunk_off.push_back(0);
-    return;
-  }
-  chunkify_maximize_chunk_size((uint32_t)batchable.size(), 16, p.chunk_off);
-}
-
-// Plan of one bls_gpu_verify_same_message call over the verify pass: every set is a
-// one-set batchable request (request index == set index, so a failing job's fallback gives
-// the one-set path's verdicts), every job of >= 2 sets is a caller-defined chunk -- ONE
-// random-scalar batch whatever its size, not chunked at 16 -- and a 1-set job is a request
-// verified on its own directly.
-struct SameMsgPlan {
-  BatchPlan plan;
-};
-
-// shape checks of the caller's batch: nullptr, or what is wrong (the call returns -2)
-static inline const char* check_same_message(const bls_same_msg_batch* in, const int32_t* set_verdicts) {
-  if (!in->job_set_offsets || !in->messages || !in->pk_indices || !in->signatures || !set_verdicts)
-    return "a required pointer is NULL";
-  if (in->job_set_offsets[0] != 0 || in->job_set_offsets[in->n_jobs] != in->n_sets)
-    return "job_set_offsets must run from 0 to n_sets";
-  for (uint32_t j = 0; j < in->n_jobs; ++j) {
-    const uint32_t beg = in->job_set_offsets[j], end = in->job_set_offsets[j + 1];
-    if (end <= beg || end > in->n_sets) return "empty job or offsets not monotone";
-    if (end - beg > BLS_SAME_MSG_MAX_JOB) return "job of more than BLS_SAME_MSG_MAX_JOB sets";
-  }
-  return nullptr;
-}
-
-static inline void plan_same_message(const bls_same_msg_batch* in, SameMsgPlan& p) {
-  p.plan.chunk_off.assign(1, 0);
-  p.plan.chunk_reqs.clear();
-  p.plan.nonbatch_reqs.clear();
-  for (uint32_t j = 0; j < in->n_jobs; ++j) {
-    const uint32_t beg = in->job_set_offsets[j], end = in->job_set_offsets[j + 1];
-    if (end - beg == 1) {
-      p.plan.nonbatch_reqs.push_back(beg);
-      continue;
-    }
-    for (uint32_t i = beg; i < end; ++i) p.plan.chunk_reqs.push_back(i);
-    p.plan.chunk_off.push_back((uint32_t)p.plan.chunk_reqs.size());
-  }
-}
-
-// Signing-root dedup for stage_pre: uniq = the first set of each distinct 32-byte
-// root (in set order), rep[i] = that first set for set i.  Committee-shared roots
-// (~512 attesters per root) then pay hash_to_field + SSWU once.
-// Open addressing over a mix of all 32 bytes, so crafted roots cost probes, not
-// wrong answers.  Returns the number of distinct roots.
-static inline uint32_t plan_msg_dedup(const uint8_t* msgs, uint32_t n, std::vector<uint32_t>& uniq,
-                                      std::vector<uint32_t>& rep) {
-  uniq.clear();
-  rep.resize(n);
-  uint32_t cap = 16;
-  while (cap < 2 * n) cap <<= 1;
-  std::vector<uint32_t> slot(cap, 0xffffffffu);
-  for (uint32_t i = 0; i < n; ++i) {
-    const uint8_t* m = msgs + 32ull * i;
-    uint64_t h = 0x9e3779b97f4a7c15ull;
-    for (int w = 0; w < 4; ++w) {
-      uint64_t v;
-      memcpy(&v, m + 8 * w, 8);
-      h = (h ^ v) * 0xff51afd7ed558ccdull;
-      h ^= h >> 32;
-    }
-    uint32_t pos = (uint32_t)h & (cap - 1);
-    for (;;) {
-      const uint32_t j = slot[pos];
-      if (j == 0xffffffffu) {
-        slot[pos] = i;
-        rep[i] = i;
-        uniq.push_back(i);
-        break;
-      }
-      if (memcmp(msgs + 32ull * j, m, 32) == 0) {
-        rep[i] = j;
-        break;
-      }
-      pos = (pos + 1) & (cap - 1);
-    }
-  }
-  return (uint32_t)uniq.size();
-}
-
-// Fill verdicts / stats from chunk results and the individual pass.
-static inline void assemble_verdicts(const bls_batch* in, const BatchPlan& p, const int32_t* chunk_ok,
-                                     const std::vector<uint32_t>& indiv_reqs, const int32_t* indiv_verdict,
-                                     int32_t* verdicts, bls_stats* stats) {
-  uint32_t n_chunks = (uint32_t)p.chunk_off.size() - 1;
-  uint32_t retries = 0, sigs_ok = 0;
-  for (uint32_t c = 0; c < n_chunks; ++c) {
-    if (chunk_ok[c] == 1) {
-      for (uint32_t k = p.chunk_off[c]; k < p.chunk_off[c + 1]; ++k) {
-        uint32_t r = p.chunk_reqs[k];
-        verdicts[r] = 1;
-        sigs_ok += in->req_set_offsets[r + 1] - in->req_set_offsets[r];
-      }
-    } else {
-      ++retries;
-    }
-  }
-  for (size_t t = 0; t < indiv_reqs.size(); ++t) verdicts[indiv_reqs[t]] = indiv_verdict[t];
-  if (stats) {
-    stats->batch_retries = retries;
-    stats->batch_sigs_success = sigs_ok;
-    stats->n_chunks = n_chunks;
-    stats->n_individual = (uint32_t)indiv_reqs.size();
-  }
-}
-
-}  // namespace bls
+// The host-side planning that used to end this header is bls/plan.hpp; sources written
+// against the earlier layout still reach it through here.
+#include "plan.hpp"

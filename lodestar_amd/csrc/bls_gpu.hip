@@ -1,25 +1,37 @@
 // MI355X (gfx950) BLS12-381 signature-set verifier: host orchestration and the
-// C-ABI declared in include/lodestar_bls.h.  Kernels: lodestar_amd/csrc/kernels/*.hip.
+// C-ABI declared in include/lodestar_bls.h.  Kernels: lodestar_amd/csrc/kernels/*.hip;
+// single-lane bodies in bls/pipeline.hpp, host-side plans in bls/plan.hpp (both shared with
+// the CPU test harness); cooperative programs from tools/gen_coop.py.
 //
-// Pipeline of one bls_gpu_verify call (single-lane bodies in bls/pipeline.hpp,
-// shared with the CPU test harness; cooperative programs from tools/gen_coop.py):
-//   H2D (one packed copy from pinned staging)
-//   k_pk     pubkey deserialize / device-table aggregation   one lane per set
-//   k_pre    SSWU points q0, q1 of H(m); signature decode    three lanes per set
-//   k_pset   H(m), G2 subgroup test, r pk, r g1,             one wavefront per set
-//            f_i = ML(r pk, H) ML(-r g1, sig)                 (k_psetn: 3 sets per wavefront
-//                                                              from 512 sets per call)
-//   (k_exact: complete formulas for the rare flagged sets, launched with a redo of
-//    k_status / k_chunk only when k_pset counted any)
-//   k_status per-request error precedence
-//   k_chunk  per chunk of >= 16 batchable requests: FE(prod f_i) == 1   (wavefront)
-//   D2H chunk verdicts -> host plans the per-request fallback
-//   k_indiv  failed chunks' requests + non-batchable requests          (wavefront)
-// All kernels of a call run on the context's stream; the host waits twice
-// (chunk verdicts, final verdicts).
-// bls_gpu_verify_same_message runs the same pass with a plan of its own (every job one
-// chunk and one Miller-loop unit) on the aggregated-signature path, its sums by k_smsum
-// (kernels/k_smsg.hip); DESIGN.md section 3 "Same-message calls".
+// Every verify entry point (bls_gpu_verify, _verify_many, _verify_same_message, _partial)
+// is one VerifyPass (below): plan_pass fixes its shape and plans, then verify_body calls
+// its stages in order.  The inputs sit in pinned mapped staging memory (no H2D copy), all
+// kernels run on the context's stream, and the host waits after the first pass and after
+// each fallback round.
+//   k_pk, k_pre   pubkey decode / table aggregation; SSWU points of H(m), signature decode
+//   first pass, one of two shapes (use_sigagg):
+//     per set     k_pset (k_psetn: up to 3 sets per wavefront): H(m), G2 subgroup test,
+//                 r pk, r g1, f_i = ML(r pk, H) ML(-r g1, sig), one wavefront per set
+//     aggregated  k_chain (per-set chains, one lane each), then the signature sums into
+//                 virtual sets -- k_gsum levels + k_vset per chunk, or ONE sum for the pass
+//                 (use_total) by k_gsum or the Pippenger k_msm, or k_smsum per same-message
+//                 job -- then the Miller-loop units' sums r_i pk_i per shared root (k_gsum1 +
+//                 k_uset), then every Miller loop in one launch (k_mln)
+//   k_status      per-request error precedence
+//   merged check  FE(prod of every f) == 1 by one k_fprod tree, when every request is
+//                 batchable and there are >= 2 chunks
+// and, as far as the pass has to go down the fallback ladder:
+//   flagged redo  k_exact (complete formulas) for the rare sets the cooperative kernels
+//                 flagged, then k_status and the merged check again
+//   chunk checks  no merged check, or it failed: (the chunks' own sums and Miller loops,
+//                 when the first pass summed once,) FE per chunk by k_chunk_coop / _simt
+//   individual    the non-batchable and the failed chunks' requests: their own Miller
+//                 loops and signature sums, k_fold, k_indiv_coop / _simt
+//   group tests   failed chunks of >= group_test_min requests: k_group_coop over bit groups
+//                 instead of one final exponentiation per request (verify_groups)
+// A partial call (one shard of a sharded call) stops after the status and returns the
+// product of its f.  DESIGN.md section 3 describes each step and the measurements behind
+// the thresholds.
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
 #include <stdio.h>
@@ -33,12 +45,12 @@
 #include <zlib.h>
 
 #include <atomic>
-#include <functional>
 #include <mutex>
 #include <string>
 #include <vector>
 
 #include "bls/group_decode.hpp"
+#include "bls/plan.hpp"
 #include "launchers.hpp"
 
 using namespace bls;
@@ -58,7 +70,7 @@ struct bls_gpu_ctx {
   uint32_t table_n, table_cap;
   uint32_t debug_flags;  // bls_gpu_set_debug_flags
   // the context's last pass failed its merged check: its next pass keeps the per-set
-  // [r] sig chains rather than the Pippenger sum (verify_body use_msm), so a failure
+  // [r] sig chains rather than the Pippenger sum (plan_pass: PassShape::use_msm), so a failure
   // there does not relaunch them (profiles/r05_ab_msm_min.json)
   bool last_merged_failed;
   // grow-only device workspace and pinned staging
@@ -650,11 +662,7 @@ int bls_gpu_validate_pubkeys(bls_gpu_ctx* ctx, const uint8_t* pks, uint32_t n, u
   return 0;
 }
 
-// One verifyManySignatureSets call (partial_out == nullptr), or the Miller-loop
-// partial of one shard of a sharded call (bls_gpu_partial): the same front half
-// (decode, hash_to_G2, per-set programs, exact path, status), then either the
-// chunk / individual verdicts or a product tree of every f_i.
-// Aggregated-signature path (k_chain + k_gsum + k_vset + k_mln single-pair Miller
+// Which first pass a call takes.  Aggregated-signature path (k_chain + k_gsum + k_vset + k_mln single-pair Miller
 // loops, one signature Miller loop per chunk) from SIGAGG_MIN_SETS sets on, except for
 // calls of at most PERSET_MAX_CALL sets while the process has at most
 // $BLS_PERSET_MAX_INFLIGHT (20,480) sets in flight (this call's included): those run the
@@ -731,20 +739,14 @@ static uint32_t group_test_min(const bls_gpu_ctx* ctx) {
   return (ctx->debug_flags & BLS_DEBUG_GROUP_TEST) ? 4u : v;
 }
 
-// Group sums (aggregated path): the tests' own signature sums, sum of r_i sig_i over
-// their requests' sets, paired ML(-g1, .) into sum_f[g] before k_group_coop; returns 0,
-// 1 when the plan does not fit the workspace (the caller tests the requests alone), < 0
-// on an error.  Unset: each request's product already holds its own sum's pairing.
-typedef std::function<int(const std::vector<uint32_t>&, const std::vector<uint32_t>&)> GroupSums;
-
-// group sums (run_group_tests) for a pass with at least $BLS_GROUP_SUMS_MIN (512)
-// group-tested requests; 0 = always, $BLS_GROUP_SUMS=0 = never.  They save Miller loops
+// group sums (VerifyPass::group_sums) for a pass with at least $BLS_GROUP_SUMS_MIN (512)
+// group-tested requests; 0 = always, $BLS_GROUP_SUMS=0 = never (SIZE_MAX).  They save Miller loops
 // (cfg4 per-set requests, ~1,300 group-tested requests a pass: 1.52M -> 1.56M sets/s
 // steady) but put a sum + Miller-loop stage in front of each round of tests, where the
 // per-request sums ride in the requests' Miller-loop launch: with a few failed chunks
 // a pass (the cfg5 slice, ~80 requests) that latency costs more (3.29M -> 3.05M)
 // (profiles/r06_ab_group_sums.json)
-static bool group_sums_on(size_t n_group_tested) {
+static size_t group_sums_min() {
   static const bool on = [] {
     const char* e = getenv("BLS_GROUP_SUMS");
     return !(e && atoi(e) == 0);
@@ -753,7 +755,7 @@ static bool group_sums_on(size_t n_group_tested) {
     const char* e = getenv("BLS_GROUP_SUMS_MIN");
     return e ? (size_t)strtoull(e, nullptr, 10) : (size_t)512;
   }();
-  return on && n_group_tested >= min_reqs;
+  return on ? min_reqs : SIZE_MAX;
 }
 
 // complement inference in the group tests (verify_groups): pass A carries each chunk's
@@ -769,162 +771,6 @@ static int group_eq_mode() {
   }();
   return mode;
 }
-static bool group_eq_on() { return group_eq_mode() != 0; }
-
-// run the tests (goff: offsets into gmem, indices into the indiv list); results in gv
-// (bit 0: passed; bit 1, with ref: its final exponentiation equals test ref[g]'s);
-// 1 when the group sums do not fit (nothing ran)
-static hipError_t pass_wait(bls_gpu_ctx* ctx, hipStream_t s);  // below, before verify_body
-
-static int run_group_tests(bls_gpu_ctx* ctx, const PipeBufs& b, GroupBufs& g, const std::vector<uint32_t>& goff,
-                           const std::vector<uint32_t>& gmem, std::vector<int32_t>& gv, hipStream_t s,
-                           const GroupSums* sums, const std::vector<uint32_t>* ref = nullptr) {
-  gv.assign(goff.size() - 1, 0);
-  if (gv.empty()) return 0;
-  if (sums && *sums) {
-    const int rc = (*sums)(goff, gmem);
-    if (rc != 0) return rc;
-  }
-  stage_copy(ctx, g.off, goff.data(), sizeof(uint32_t) * goff.size());  // the stream is idle
-  stage_copy(ctx, g.members, gmem.data(), sizeof(uint32_t) * gmem.size());
-  g.n = (uint32_t)gv.size();
-  GroupBufs gg = g;
-  if (ref) stage_copy(ctx, g.ref, ref->data(), sizeof(uint32_t) * ref->size());
-  else gg.fe = nullptr;
-  HIPC(ctx, launch_k_group_coop(b, ctx->coop, gg, s)); dbg_sync(s, "k_group_coop");
-  HIPC(ctx, pass_wait(ctx, s));
-  memcpy(gv.data(), res_host(ctx, g.verdict), sizeof(int32_t) * gv.size());
-  return 0;
-}
-
-struct GtChunk {
-  uint32_t beg, end;  // its requests in the indiv list
-  uint32_t ch;        // its chunk (b.chunk_fe)
-};
-
-static int verify_groups(bls_gpu_ctx* ctx, const PipeBufs& b, GroupBufs& gbufs, const std::vector<GtChunk>& chunks,
-                         std::vector<int32_t>& verdict, hipStream_t s, size_t grp_cap, size_t grp_mem_cap,
-                         const GroupSums* sums) {
-  struct Chunk {
-    std::vector<uint32_t> ok;  // indiv indices of the requests of status OK
-    bool has_err = false;
-    bool whole = false;        // a test of all of ok at `first` (else the chunk check's value)
-    uint32_t first = 0, nbits = 0;
-    int32_t b = -1;            // the one invalid request's position in ok (pass B), -1 none
-  };
-  std::vector<Chunk> cs;
-  std::vector<uint32_t> goff{0}, gmem, ref;
-  const bool eq = group_eq_on() && gbufs.fe;
-  auto add_test = [&](const std::vector<uint32_t>& m, uint32_t r) {
-    gmem.insert(gmem.end(), m.begin(), m.end());
-    goff.push_back((uint32_t)gmem.size());
-    ref.push_back(r);
-  };
-  for (const auto& ch : chunks) {
-    Chunk c;
-    for (uint32_t t = ch.beg; t < ch.end; ++t) {
-      if (verdict[t] == 2) c.ok.push_back(t);
-      else c.has_err = true;  // its -code stays
-    }
-    if (c.ok.empty()) continue;
-    c.first = (uint32_t)goff.size() - 1;
-    // the whole's value: the failed chunk check's own final exponentiation when it ran
-    // over exactly these requests (no erroneous one), else a test of them
-    const bool from_check = eq && group_eq_mode() != 2 && gbufs.ref_fe && !c.has_err && c.ok.size() > 1;
-    c.whole = !from_check && (eq || c.has_err || c.ok.size() == 1);
-    if (c.whole) add_test(c.ok, REF_NONE);
-    const uint32_t m = (uint32_t)c.ok.size();
-    while (m > 1 && (1u << c.nbits) < m) ++c.nbits;
-    for (uint32_t j = 0; j < c.nbits; ++j) {
-      std::vector<uint32_t> g;
-      for (uint32_t k = 0; k < m; ++k)
-        if ((k >> j) & 1u) g.push_back(c.ok[k]);
-      add_test(g, from_check ? (REF_CHUNK | ch.ch) : c.first);
-    }
-    cs.push_back(std::move(c));
-  }
-  if (gmem.size() > grp_mem_cap || goff.size() - 1 > grp_cap) {
-    snprintf(ctx->err, sizeof(ctx->err), "group-test plan exceeds its workspace");
-    return -3;
-  }
-  std::vector<int32_t> gv;
-  std::vector<uint32_t> goff_b{0}, gmem_b, alone;  // alone: requests for pass C
-  std::vector<size_t> in_b;
-  const int rc_a = run_group_tests(ctx, b, gbufs, goff, gmem, gv, s, sums, eq ? &ref : nullptr);
-  if (rc_a < 0) return -1;
-  if (rc_a == 1) {  // the group sums of pass A do not fit: every request alone
-    for (const Chunk& c : cs) alone.insert(alone.end(), c.ok.begin(), c.ok.end());
-    cs.clear();
-  }
-  // complement inference: with the test of all the chunk's requests (A) beside each bit
-  // group G_j, FE(G_j) FE(rest_j) = FE(A) decides the complement too (FE(rest_j) == 1 iff
-  // FE(G_j) == FE(A)), so a single invalid request b shows as exactly one failing test per
-  // bit -- G_j where b's bit j is set, rest_j where it is clear -- and every other request
-  // sits in a passing test: no pass B.  Both G_j and rest_j failing (two or more invalid)
-  // or an index past m: pass C.
-  for (size_t i = 0; eq && i < cs.size(); ++i) {
-    const Chunk& c = cs[i];
-    const uint32_t m = (uint32_t)c.ok.size();
-    // without a whole test the whole is the failed chunk check (it failed)
-    const bool pass = c.whole && (gv[c.first] & 1) != 0;
-    const int32_t bad = group_decode(m, c.nbits, pass, gv.data() + c.first + (c.whole ? 1u : 0u));
-    if (bad < 0) {
-      alone.insert(alone.end(), c.ok.begin(), c.ok.end());
-      continue;
-    }
-    for (uint32_t k = 0; k < m; ++k) verdict[c.ok[k]] = (int32_t)k == bad ? 0 : 1;
-  }
-  if (eq) cs.clear();
-  // decode pass A; plan pass B
-  for (size_t i = 0; i < cs.size(); ++i) {
-    Chunk& c = cs[i];
-    uint32_t idx = c.first;
-    const uint32_t m = (uint32_t)c.ok.size();
-    if (c.has_err || m == 1) {
-      const bool pass = gv[idx++] == 1;
-      if (pass || m == 1) {
-        for (uint32_t t : c.ok) verdict[t] = pass ? 1 : 0;
-        continue;
-      }
-    }
-    uint32_t bad = 0;
-    for (uint32_t j = 0; j < c.nbits; ++j)
-      if (gv[idx + j] != 1) bad |= 1u << j;
-    if (bad >= m) {
-      alone.insert(alone.end(), c.ok.begin(), c.ok.end());
-      continue;
-    }
-    c.b = (int32_t)bad;
-    gmem_b.push_back(c.ok[bad]);
-    goff_b.push_back((uint32_t)gmem_b.size());
-    for (uint32_t k = 0; k < m; ++k)
-      if (k != bad) gmem_b.push_back(c.ok[k]);
-    goff_b.push_back((uint32_t)gmem_b.size());
-    in_b.push_back(i);
-  }
-  const int rc_b = in_b.empty() ? 0 : run_group_tests(ctx, b, gbufs, goff_b, gmem_b, gv, s, sums);
-  if (rc_b < 0) return -1;
-  for (size_t q = 0; q < in_b.size(); ++q) {
-    Chunk& c = cs[in_b[q]];
-    if (rc_b == 0 && gv[2 * q] == 0 && gv[2 * q + 1] == 1) {
-      for (uint32_t k = 0; k < c.ok.size(); ++k) verdict[c.ok[k]] = (int32_t)k == c.b ? 0 : 1;
-    } else {
-      alone.insert(alone.end(), c.ok.begin(), c.ok.end());
-    }
-  }
-  // pass C: one test per request
-  std::vector<uint32_t> goff_c{0};
-  for (size_t k = 0; k < alone.size(); ++k) goff_c.push_back((uint32_t)k + 1);
-  const int rc_c = run_group_tests(ctx, b, gbufs, goff_c, alone, gv, s, sums);
-  if (rc_c != 0) {
-    // one request per test always fits the request-sum workspace
-    snprintf(ctx->err, sizeof(ctx->err), "group tests: per-request sums do not fit");
-    return -3;
-  }
-  for (size_t k = 0; k < alone.size(); ++k) verdict[alone[k]] = gv[k] == 1 ? 1 : 0;
-  return 0;
-}
-
 
 // Pippenger merged signature sum (k_msm) instead of the per-set [r] sig chains (k_chain
 // role 2, ~1.6k Fp products per set) and the k_gsum levels: ~10 % fewer instructions per
@@ -984,221 +830,6 @@ static bool merged_skip_after_fail() {
   return on;
 }
 
-// Segmented-sum plan for k_gsum over groups of requests: the groups' set indices
-// (group-major) and, per level, (beg, end) segments of at most GSUM_FAN items that
-// never straddle a group; level 0 indexes gsets, level L > 0 the outputs of level
-// L - 1.  After the last level there is one point per group, in group order.
-struct GsumPlan {
-  std::vector<uint32_t> gsets;
-  std::vector<uint32_t> seg;        // every level's pairs, concatenated
-  std::vector<uint32_t> level_off;  // level L: pairs [level_off[L], level_off[L + 1])
-};
-
-// groups given as explicit set lists: group g = sets[goff[g] .. goff[g + 1])
-static void plan_gsum_sets(const std::vector<uint32_t>& goff, const std::vector<uint32_t>& sets, GsumPlan& p) {
-  p.gsets = sets;
-  p.seg.clear();
-  p.level_off.assign(1, 0);
-  const size_t G = goff.size() - 1;
-  std::vector<uint32_t> cnt(G);
-  for (size_t g = 0; g < G; ++g) {
-    const uint32_t gb = goff[g], ge = goff[g + 1];
-    cnt[g] = 0;
-    for (uint32_t k = gb; k < ge || (k == gb && gb == ge); k += GSUM_FAN) {
-      p.seg.push_back(k);
-      p.seg.push_back(k + GSUM_FAN < ge ? k + GSUM_FAN : ge);
-      ++cnt[g];
-      if (gb == ge) break;
-    }
-  }
-  p.level_off.push_back((uint32_t)(p.seg.size() / 2));
-  for (;;) {
-    bool more = false;
-    for (uint32_t c : cnt) more = more || c > 1;
-    if (!more) break;
-    uint32_t pos = 0;
-    for (size_t g = 0; g < G; ++g) {
-      const uint32_t c = cnt[g];
-      uint32_t nc = 0;
-      for (uint32_t k = 0; k < c; k += GSUM_FAN, ++nc) {
-        p.seg.push_back(pos + k);
-        p.seg.push_back(pos + (k + GSUM_FAN < c ? k + GSUM_FAN : c));
-      }
-      pos += c;
-      cnt[g] = nc;
-    }
-    p.level_off.push_back((uint32_t)(p.seg.size() / 2));
-  }
-}
-
-// groups of requests (chunks, individually verified requests): their sets in order
-static void plan_gsum(const bls_batch* in, const std::vector<uint32_t>& grp_off, const std::vector<uint32_t>& grp_reqs,
-                      GsumPlan& p) {
-  std::vector<uint32_t> goff(1, 0), sets;
-  for (size_t g = 0; g + 1 < grp_off.size(); ++g) {
-    for (uint32_t k = grp_off[g]; k < grp_off[g + 1]; ++k) {
-      const uint32_t r = grp_reqs[k];
-      for (uint32_t i = in->req_set_offsets[r]; i < in->req_set_offsets[r + 1]; ++i) sets.push_back(i);
-    }
-    goff.push_back((uint32_t)sets.size());
-  }
-  plan_gsum_sets(goff, sets, p);
-}
-
-// Miller-loop units (sum r_i pk_i per root): within each chunk, the sets
-// signing the same root (msg_rep: the root's first set) form one unit, paired once as
-// ML(sum r_i pk_i, H(root)).  Used when it at least halves the chunks' Miller loops.
-struct UnitPlan {
-  std::vector<uint32_t> set_unit, unit_rep, unit_off, goff, members;
-  uint32_t n_units = 0;
-};
-
-static bool plan_units(const bls_batch* in, const BatchPlan& plan, const std::vector<uint32_t>& msg_rep, uint32_t n,
-                       UnitPlan& u) {
-  const uint32_t C = (uint32_t)plan.chunk_off.size() - 1;
-  if (msg_rep.empty() || C == 0) return false;
-  u.set_unit.assign(n, UNIT_NONE);
-  u.unit_off.assign(1, 0);
-  std::vector<uint32_t> stamp(n, 0xFFFFFFFFu), unit_of(n, 0);
-  std::vector<std::vector<uint32_t>> mem;
-  uint32_t in_chunks = 0;
-  for (uint32_t c = 0; c < C; ++c) {
-    for (uint32_t k = plan.chunk_off[c]; k < plan.chunk_off[c + 1]; ++k) {
-      const uint32_t r = plan.chunk_reqs[k];
-      for (uint32_t i = in->req_set_offsets[r]; i < in->req_set_offsets[r + 1]; ++i) {
-        const uint32_t rep = msg_rep[i];
-        if (stamp[rep] != c) {
-          stamp[rep] = c;
-          unit_of[rep] = (uint32_t)mem.size();
-          mem.emplace_back();
-          u.unit_rep.push_back(rep);
-        }
-        u.set_unit[i] = unit_of[rep];
-        mem[unit_of[rep]].push_back(i);
-        ++in_chunks;
-      }
-    }
-    u.unit_off.push_back((uint32_t)mem.size());
-  }
-  u.n_units = (uint32_t)mem.size();
-  if (2ull * u.n_units > in_chunks) return false;
-  u.goff.assign(1, 0);
-  u.members.clear();
-  for (auto& m : mem) {
-    u.members.insert(u.members.end(), m.begin(), m.end());
-    u.goff.push_back((uint32_t)u.members.size());
-  }
-  return true;
-}
-
-// Launch the levels of `p` (seg: its pairs on the device) and k_vset for groups
-// [vbase, vbase + G); tmp: two point buffers of level-0 size.
-static int launch_gsum(bls_gpu_ctx* ctx, PipeBufs& b, const GsumPlan& p, const uint32_t* seg_dev,
-                       const uint32_t* gsets_dev, G2J* const tmp[2], uint32_t vbase, hipStream_t s) {
-  b.gsets = gsets_dev;
-  const size_t levels = p.level_off.size() - 1;
-  const G2J* in = nullptr;
-  for (size_t L = 0; L < levels; ++L) {
-    const uint32_t beg = p.level_off[L], n_seg = p.level_off[L + 1] - beg;
-    HIPC(ctx, launch_k_gsum(b, seg_dev + 2 * beg, n_seg, in, tmp[L & 1], s)); dbg_sync(s, "k_gsum");
-    in = tmp[L & 1];
-  }
-  const uint32_t G = levels ? p.level_off[levels] - p.level_off[levels - 1] : 0;
-  HIPC(ctx, launch_k_vset(b, in, G, vbase, s)); dbg_sync(s, "k_vset");
-  return 0;
-}
-
-// plan_batch over several worker messages submitted together (bls_gpu_verify_many):
-// each message's batchable requests are chunked on their own (worker.ts:56 runs per
-// message), so the chunks never straddle a message; req_bounds[k] = first request of
-// message k, req_bounds[n_msgs] = n_reqs.
-static void plan_batch_msgs(const bls_batch* in, const std::vector<uint32_t>& req_bounds, BatchPlan& p) {
-  p.chunk_off.assign(1, 0);
-  p.chunk_reqs.clear();
-  p.nonbatch_reqs.clear();
-  std::vector<uint32_t> batchable, bounds;
-  for (size_t m = 0; m + 1 < req_bounds.size(); ++m) {
-    batchable.clear();
-    for (uint32_t r = req_bounds[m]; r < req_bounds[m + 1]; ++r) {
-      if (in->req_batchable && in->req_batchable[r]) batchable.push_back(r);
-      else p.nonbatch_reqs.push_back(r);
-    }
-    if (batchable.empty()) continue;
-    chunkify_maximize_chunk_size((uint32_t)batchable.size(), 16, bounds);
-    const uint32_t base = (uint32_t)p.chunk_reqs.size();
-    p.chunk_reqs.insert(p.chunk_reqs.end(), batchable.begin(), batchable.end());
-    for (size_t k = 1; k < bounds.size(); ++k) p.chunk_off.push_back(base + bounds[k]);
-  }
-}
-
-// Host-side shape checks of one caller batch (0, or -2 with ctx->err).  The kernels and
-// the verify_many join index sets and key lists through these offsets, so they must
-// start at 0, be monotone and end at the array sizes.
-static int check_batch(bls_gpu_ctx* ctx, const bls_batch* in, const char* what) {
-  const uint32_t n = in->n_sets, R = in->n_reqs;
-  if (R == 0) return 0;
-  if (!in->req_set_offsets) {
-    snprintf(ctx->err, sizeof(ctx->err), "%s: req_set_offsets missing", what);
-    return -2;
-  }
-  if (in->req_set_offsets[0] != 0 || in->req_set_offsets[R] != n) {
-    snprintf(ctx->err, sizeof(ctx->err), "%s: req_set_offsets must run from 0 to n_sets", what);
-    return -2;
-  }
-  if (in->set_pk_offsets == nullptr && in->pubkeys == nullptr && n > 0) {
-    snprintf(ctx->err, sizeof(ctx->err), "%s: no pubkeys given", what);
-    return -2;
-  }
-  if (n > 0 && (!in->messages || !in->signatures)) {
-    snprintf(ctx->err, sizeof(ctx->err), "%s: messages / signatures missing", what);
-    return -2;
-  }
-  for (uint32_t r = 0; r < R; ++r) {
-    if (in->req_set_offsets[r] > in->req_set_offsets[r + 1]) {
-      snprintf(ctx->err, sizeof(ctx->err), "%s: req_set_offsets not monotone at %u", what, r);
-      return -2;
-    }
-  }
-  if (in->set_pk_offsets) {
-    if (in->set_pk_offsets[0] != 0) {
-      snprintf(ctx->err, sizeof(ctx->err), "%s: set_pk_offsets[0] != 0", what);
-      return -2;
-    }
-    for (uint32_t i = 0; i < n; ++i) {
-      if (in->set_pk_offsets[i] > in->set_pk_offsets[i + 1]) {
-        snprintf(ctx->err, sizeof(ctx->err), "%s: set_pk_offsets not monotone at %u", what, i);
-        return -2;
-      }
-    }
-    if (in->set_pk_offsets[n] > 0 && !in->pk_indices) {
-      snprintf(ctx->err, sizeof(ctx->err), "%s: pk_indices missing", what);
-      return -2;
-    }
-  }
-  return 0;
-}
-
-// The Miller-loop units of a same-message call (bls/pipeline.hpp plan_same_message): unit
-// c = all the sets of chunk c, paired once as e(sum r_i pk_i, H(root)); rep = the set that
-// computed the root's H (plan_msg_dedup's first set of the root; without dedup the job's
-// own first set)
-static void units_same_message(const BatchPlan& plan, const std::vector<uint32_t>& msg_rep, uint32_t n, UnitPlan& u) {
-  const uint32_t C = (uint32_t)plan.chunk_off.size() - 1;
-  u.set_unit.assign(n, UNIT_NONE);
-  u.unit_off.resize(C + 1);
-  u.unit_rep.resize(C);
-  u.goff = plan.chunk_off;
-  u.members = plan.chunk_reqs;  // (every request is one set: request index == set index)
-  for (uint32_t c = 0; c < C; ++c) {
-    u.unit_off[c] = c;
-    const uint32_t first = plan.chunk_reqs[plan.chunk_off[c]];
-    u.unit_rep[c] = msg_rep.empty() ? first : msg_rep[first];
-    for (uint32_t k = plan.chunk_off[c]; k < plan.chunk_off[c + 1]; ++k) u.set_unit[plan.chunk_reqs[k]] = c;
-  }
-  u.unit_off[C] = C;
-  u.n_units = C;
-}
-
 struct InFlight {
   uint64_t n;
   explicit InFlight(uint64_t k) : n(k) { g_sets_in_flight.fetch_add(n, std::memory_order_relaxed); }
@@ -1233,233 +864,312 @@ static hipError_t pass_wait(bls_gpu_ctx* ctx, hipStream_t s) {
   return e;
 }
 
-static int verify_body(bls_gpu_ctx* ctx, const bls_batch* in, int32_t* verdicts, bls_stats* stats,
-                       uint32_t scalar_base, uint8_t* partial_out, int32_t* partial_status, uint32_t* partial_err,
-                       const std::vector<uint32_t>* req_bounds, const SameMsgPlan* sm);
+}  // extern "C"
 
-// One call under the context's lock.  A call that fails part-way may leave the MSM's
-// bucket counters / tickets (reset only by the kernels' last workgroups) mid-pass: they
-// are zeroed again before the context takes another call.
-static int verify_impl(bls_gpu_ctx* ctx, const bls_batch* in, int32_t* verdicts, bls_stats* stats,
-                       uint32_t scalar_base, uint8_t* partial_out, int32_t* partial_status,
-                       uint32_t* partial_err = nullptr, const std::vector<uint32_t>* req_bounds = nullptr,
-                       const SameMsgPlan* sm = nullptr) {
-  CTX_LOCK(ctx);
-  ctx->wait_block = wait_blocks(in->n_sets);
-  const int rc = verify_body(ctx, in, verdicts, stats, scalar_base, partial_out, partial_status, partial_err,
-                             req_bounds, sm);
-  if (rc < 0 && ctx->msm_state) {
-    (void)hipStreamSynchronize(ctx->stream);
-    (void)hipMemsetAsync(ctx->msm_state, 0, sizeof(uint32_t) * MSM_STATE_WORDS, ctx->stream);
-    (void)hipStreamSynchronize(ctx->stream);
+// ---------------------------------------------------------------------------
+// The verify pass
+// ---------------------------------------------------------------------------
+namespace {
+
+// The k_fprod product tree over in[0, m): levels of FPROD_FAN through the two buffers t.
+// With `verdict` the levels stop at FPROD_FAN elements and the last launch writes
+// FE(product) == 1 there; without it they run down to one element, left at *out.
+int fprod_tree(bls_gpu_ctx* ctx, const Fp12* in, uint32_t m, Fp12* const t[2], int32_t* verdict, const Fp12** out,
+               hipStream_t s) {
+  const uint32_t stop = verdict ? FPROD_FAN : 1u;
+  const Fp12* cur = in;
+  for (uint32_t lvl = 0; m > stop; ++lvl) {
+    HIPC(ctx, launch_k_fprod(cur, m, t[lvl & 1], nullptr, ctx->coop, s)); dbg_sync(s, "k_fprod");
+    cur = t[lvl & 1];
+    m = (m + FPROD_FAN - 1) / FPROD_FAN;
   }
-  return rc;
+  if (verdict) {
+    HIPC(ctx, launch_k_fprod(cur, m, nullptr, verdict, ctx->coop, s)); dbg_sync(s, "k_fprod verdict");
+  }
+  if (out) *out = cur;
+  return 0;
 }
 
-static int verify_body(bls_gpu_ctx* ctx, const bls_batch* in, int32_t* verdicts, bls_stats* stats,
-                       uint32_t scalar_base, uint8_t* partial_out, int32_t* partial_status, uint32_t* partial_err,
-                       const std::vector<uint32_t>* req_bounds, const SameMsgPlan* sm) {
-  const bool partial = partial_out != nullptr;
-  HIPC(ctx, hipSetDevice(ctx->device));
-  const uint32_t n = in->n_sets, R = in->n_reqs;
-  if (stats) memset(stats, 0, sizeof(*stats));
-  if (R == 0) return 0;
-  if (const int rc = check_batch(ctx, in, "batch")) return rc;
-  const InFlight in_flight(n);
-  BatchPlan plan;
-  if (sm) plan = sm->plan;  // every job a caller-defined chunk (plan_same_message)
-  else if (req_bounds) plan_batch_msgs(in, *req_bounds, plan);
-  else plan_batch(in, plan);
-  std::vector<uint32_t> msg_uniq, msg_rep;
-  const uint32_t n_uniq = (ctx->debug_flags & BLS_DEBUG_NO_MSG_DEDUP) ? n : plan_msg_dedup(in->messages, n, msg_uniq, msg_rep);
-  const bool dedup = n_uniq < n;
-  // Merged check: with only batchable requests and >= 2 chunks, first test the
-  // product of every f_i with ONE final exponentiation (k_fprod tree); it passes iff
-  // every chunk would (the same random-scalar batch, just larger), so chunk_ok is
-  // all 1 and the per-chunk final exponentiations are skipped.  A failing merged
-  // check (or a request with an error status) falls back to k_chunk_coop, so
-  // verdicts and stats stay those of the chunked worker (worker.ts:56-88).
-  const bool merged_eligible = !partial && plan.chunk_off.size() > 2 && plan.nonbatch_reqs.empty() && n > 0 &&
-                               !(ctx->debug_flags & BLS_DEBUG_NO_MERGED_CHECK);
-  // (same-message calls neither read nor write the context's merged-check history)
-  const bool merged_skipped = merged_eligible && !sm && ctx->last_merged_failed && merged_skip_after_fail() &&
-                              !(ctx->debug_flags & BLS_DEBUG_MERGED_EVERY_PASS);
-  const bool merged = merged_eligible && !merged_skipped;
-  const uint32_t n_chunks = (uint32_t)plan.chunk_off.size() - 1;
-  const uint32_t n_pk_idx = in->set_pk_offsets ? in->set_pk_offsets[n] : 0;
-  // aggregated-signature path: virtual sets n + chunk and n + n_chunks + individual
-  // request; the chunk groups' sum plan is staged with the inputs
-  // (a same-message call always: the per-set k_pset path would bring back one Miller
-  // loop pair per set)
-  const bool sigagg = n > 0 && (sm || use_sigagg(ctx, n));
-  GsumPlan chunk_gsum, unit_gsum;
-  UnitPlan units;
-  // same-message jobs: one unit per job (chunk) holding all its sets, whatever the flags
-  if (sm && n_chunks > 0) units_same_message(plan, msg_rep, n, units);
-  const bool use_units = sm ? n_chunks > 0
-                            : sigagg && dedup && !(ctx->debug_flags & BLS_DEBUG_NO_UNITS) &&
-                                  plan_units(in, plan, msg_rep, n, units);
-  // ... and their sums of r_i pk_i and r_i sig_i by k_smsum, one wavefront per job
-  const bool smsum = sm && use_units;
-  const uint32_t n_units = use_units ? units.n_units : 0;
-  // f / chain layout: sets [0, n) | chunk signature sums [n, n + C) | units
-  // [n + C, n + C + U) | individual requests' signature sums [n + C + U, .. + R)
-  const uint32_t unit_base = n + n_chunks, indiv_vbase = n + n_chunks + n_units;
-  const uint32_t n_total = sigagg ? indiv_vbase + R : n;
-  if (sigagg && !smsum) {
-    std::vector<uint32_t> goff(plan.chunk_off.begin(), plan.chunk_off.end());
-    plan_gsum(in, goff, plan.chunk_reqs, chunk_gsum);
+inline hipError_t launch_gsum_level(const PipeBufs& b, const uint32_t* seg, uint32_t n_seg, const G2J* in, G2J* out,
+                                    hipStream_t s) {
+  return launch_k_gsum(b, seg, n_seg, in, out, s);
+}
+inline hipError_t launch_gsum_level(const PipeBufs& b, const uint32_t* seg, uint32_t n_seg, const G1J* in, G1J* out,
+                                    hipStream_t s) {
+  return launch_k_gsum1(b, seg, n_seg, in, out, s);
+}
+
+// Run the levels of `p` (seg_dev: its pairs on the device) over the sets b.gsets names, G2
+// points by k_gsum or G1 points by k_gsum1; tmp: two point buffers of level-0 size.
+// *sums: one point per group, in group order.
+template <class P>
+int gsum_levels(bls_gpu_ctx* ctx, const PipeBufs& b, const GsumPlan& p, const uint32_t* seg_dev, P* const tmp[2],
+                const char* what, const P** sums, hipStream_t s) {
+  const P* in = nullptr;
+  for (size_t L = 0; L + 1 < p.level_off.size(); ++L) {
+    const uint32_t beg = p.level_off[L], n_seg = p.level_off[L + 1] - beg;
+    HIPC(ctx, launch_gsum_level(b, seg_dev + 2 * beg, n_seg, in, tmp[L & 1], s)); dbg_sync(s, what);
+    in = tmp[L & 1];
   }
-  if (use_units && !smsum) plan_gsum_sets(units.goff, units.members, unit_gsum);
-  // Merged signature sum: under the merged check the chunks' signature sums only ever
-  // meet in the product of every f, and prod_c e(-g1, S_c) = e(-g1, sum_c S_c) after the
-  // final exponentiation, so the first pass sums every chunk's r_i sig_i into ONE point
-  // (chunk group 0; the other chunk groups are empty, so k_vset gives them f = 1) and
-  // pairs it once.  A failing merged check re-sums per chunk and pairs each sum before
-  // the per-chunk final exponentiations (k_chunk_coop), so chunk verdicts are unchanged.
-  // (not for same-message jobs: each job's sum is paired in the first pass's launch)
-  const bool use_total = sigagg && !sm && merged && n_chunks > 1 && sig_total_on();
+  *sums = in;
+  return 0;
+}
+
+// what an entry point asks of the pass
+struct PassArgs {
+  int32_t* verdicts;
+  bls_stats* stats;
+  uint32_t scalar_base;
+  uint8_t* partial_out;  // non-null: the Miller-loop partial of one shard (bls_gpu_partial)
+  int32_t* partial_status;
+  uint32_t* partial_err;
+  const std::vector<uint32_t>* req_bounds;  // verify_many: the messages' first requests
+  const SameMsgPlan* sm;                    // verify_same_message: its own plan
+};
+
+// Every decision and count of a pass, fixed by plan_pass before anything is staged.
+struct PassShape {
+  uint32_t n, R, n_chunks, n_uniq, n_pk_idx;
+  bool partial, sm, dedup;
+  // Merged check: with only batchable requests and >= 2 chunks, first test the product of
+  // every f_i with ONE final exponentiation (k_fprod tree); it passes iff every chunk would
+  // (the same random-scalar batch, just larger), so chunk_ok is all 1 and the per-chunk
+  // final exponentiations are skipped.  A failing merged check (or a request with an error
+  // status) falls back to k_chunk_coop, so verdicts and stats stay those of the chunked
+  // worker (worker.ts:56-88).  merged_skipped: merged_skip_after_fail.
+  bool merged_eligible, merged_skipped, merged;
+  // aggregated-signature path (a same-message call always: the per-set k_pset path would
+  // bring back one Miller loop pair per set)
+  bool sigagg;
+  bool use_units;  // Miller-loop units; same-message jobs: one per job, whatever the flags
+  bool smsum;      // ... and their sums of r_i pk_i and r_i sig_i by k_smsum, one wavefront per job
+  // Merged signature sum: under the merged check the chunks' signature sums only ever meet
+  // in the product of every f, and prod_c e(-g1, S_c) = e(-g1, sum_c S_c) after the final
+  // exponentiation, so the first pass sums every chunk's r_i sig_i into ONE point (chunk
+  // group 0; the other chunk groups are empty, so k_vset gives them f = 1) and pairs it
+  // once.  A failing merged check re-sums per chunk and pairs each sum before the
+  // per-chunk final exponentiations, so chunk verdicts are unchanged.  (Not for
+  // same-message jobs: each job's sum is paired in the first pass's launch.)
+  bool use_total;
   // ... and under it the sum is one Pippenger MSM over the live sets (kernels/k_msm.hip)
   // instead of per-set [r] sig chains + k_gsum levels; the per-set RS are made (k_chain
   // role 2 alone) only when the merged check fails and the chunks' own sums are needed
   // (an MSM entry packs its bucket slot in 22 bits and a bucket takes up to 2 entries per
   // set: passes above MSM_MAX_SETS keep the group sums)
-  const bool use_msm = use_total && n <= MSM_MAX_SETS &&
-                       ((msm_on() && !ctx->last_merged_failed) || (ctx->debug_flags & BLS_DEBUG_MSM));
-  GsumPlan total_gsum;
-  if (use_total) {
-    std::vector<uint32_t> goff(n_chunks + 1, (uint32_t)chunk_gsum.gsets.size());
-    goff[0] = 0;
-    plan_gsum_sets(goff, chunk_gsum.gsets, total_gsum);
-  }
-  const size_t gseg_cap = 2ull * (n / 2 + 12ull * R + 8);  // uint32s: every level of any plan (fan-in >= 4)
-  const size_t gtmp_cap = n / GSUM_FAN + R + 1;                  // level-0 segments of any plan
-  if (sigagg && chunk_gsum.seg.size() > gseg_cap) {
-    snprintf(ctx->err, sizeof(ctx->err), "group-sum plan exceeds its workspace");
-    return -3;
-  }
+  bool use_msm;
+  bool ml_shared;  // k_mln shares one loop among four consecutive live items of one domain
+  // f / chain layout: sets [0, n) | chunk signature sums [n, n + C) | units
+  // [n + C, n + C + U) | individual requests' signature sums [n + C + U, .. + R)
+  uint32_t n_units, unit_base, indiv_vbase, n_total;
+  uint32_t n_prod;  // the f's of every set, chunk group and unit: what the product trees multiply
+  // group tests: the smallest chunk tested so, whether any chunk is that large (their
+  // buffers are carved only then), $BLS_GROUP_EQ, the fewest group-tested requests that
+  // take group sums (SIZE_MAX: never)
+  uint32_t gt_min;
+  bool gt_possible;
+  int gt_eq_mode;
+  size_t gsums_min;
+  // SIMT final exponentiations (kernels/k_fin_simt.hip) for a failing pass's many chunk
+  // checks / requests verified alone: 4 Fp12 per task, carved when a pass could need them
+  uint32_t fe_min;
+  bool fe_simt_possible;
+  uint32_t init_set_flag, pack, mlf_pl;  // BLS_DEBUG_FORCE_EXACT, _PACK, _MLF_PL
+  bool pl_forced;                        // a test forces the items per k_mlf lane
+  bool merged_after_fail;                // the context's last pass failed its merged check
+  size_t gseg_cap, gtmp_cap, grp_cap, grp_mem_cap;
+};
 
-  // product domain of every first-pass Miller-loop item (sets, chunk signature sums,
-  // units): k_mln shares one loop among four consecutive live items of one domain
-  const bool ml_shared = sigagg && ml_shared_on();
+// the host vectors a pass stages with its inputs (bls/plan.hpp)
+struct PassPlans {
+  BatchPlan built;  // unless the caller brought its own (same-message calls)
+  const BatchPlan* plan;
+  std::vector<uint32_t> msg_uniq, msg_rep;
+  UnitPlan units;
+  GsumPlan chunk_gsum, unit_gsum, total_gsum;
   std::vector<uint32_t> ml_dom;
-  if (ml_shared) {
-    ml_dom.assign(indiv_vbase, 0xFFFFFFFFu);
-    for (uint32_t ch = 0; ch < n_chunks; ++ch) {
-      for (uint32_t k = plan.chunk_off[ch]; k < plan.chunk_off[ch + 1]; ++k) {
-        const uint32_t r = plan.chunk_reqs[k];
-        for (uint32_t i = in->req_set_offsets[r]; i < in->req_set_offsets[r + 1]; ++i) ml_dom[i] = ch;
-      }
-      ml_dom[n + ch] = ch;
-      if (use_units)
-        for (uint32_t u = units.unit_off[ch]; u < units.unit_off[ch + 1]; ++u) ml_dom[unit_base + u] = ch;
-    }
-    for (uint32_t r : plan.nonbatch_reqs)
-      for (uint32_t i = in->req_set_offsets[r]; i < in->req_set_offsets[r + 1]; ++i) ml_dom[i] = 0x80000000u | r;
-  }
+  std::vector<uint32_t> agg_list;  // aggregate sets big enough for a wavefront each (k_pk_agg)
+};
 
-  // aggregate sets big enough for a wavefront each (k_pk_agg)
-  std::vector<uint32_t> agg_list;
+// The one place a pass reads the environment knobs, the context's debug flags and its
+// merged-check history: fills the plans and returns the shape.
+PassShape plan_pass(const bls_gpu_ctx* ctx, const bls_batch* in, const PassArgs& a, PassPlans& pl) {
+  PassShape sh;
+  memset(&sh, 0, sizeof(sh));
+  const uint32_t flags = ctx->debug_flags;
+  const uint32_t n = sh.n = in->n_sets, R = sh.R = in->n_reqs;
+  const uint32_t* req_off = in->req_set_offsets;
+  sh.partial = a.partial_out != nullptr;
+  sh.sm = a.sm != nullptr;
+  if (a.sm) {
+    pl.plan = &a.sm->plan;  // every job a caller-defined chunk (plan_same_message)
+  } else {
+    if (a.req_bounds) plan_batch_msgs(in, *a.req_bounds, pl.built);
+    else plan_batch(in, pl.built);
+    pl.plan = &pl.built;
+  }
+  const BatchPlan& plan = *pl.plan;
+  sh.n_uniq = (flags & BLS_DEBUG_NO_MSG_DEDUP) ? n : plan_msg_dedup(in->messages, n, pl.msg_uniq, pl.msg_rep);
+  sh.dedup = sh.n_uniq < n;
+  sh.merged_after_fail = ctx->last_merged_failed;
+  sh.merged_eligible = !sh.partial && plan.chunk_off.size() > 2 && plan.nonbatch_reqs.empty() && n > 0 &&
+                       !(flags & BLS_DEBUG_NO_MERGED_CHECK);
+  // (same-message calls neither read nor write the context's merged-check history)
+  sh.merged_skipped = sh.merged_eligible && !sh.sm && sh.merged_after_fail && merged_skip_after_fail() &&
+                      !(flags & BLS_DEBUG_MERGED_EVERY_PASS);
+  sh.merged = sh.merged_eligible && !sh.merged_skipped;
+  const uint32_t C = sh.n_chunks = (uint32_t)plan.chunk_off.size() - 1;
+  sh.n_pk_idx = in->set_pk_offsets ? in->set_pk_offsets[n] : 0;
+  sh.sigagg = n > 0 && (sh.sm || use_sigagg(ctx, n));
+  if (sh.sm && C > 0) units_same_message(plan, pl.msg_rep, n, pl.units);
+  sh.use_units = sh.sm ? C > 0
+                       : sh.sigagg && sh.dedup && !(flags & BLS_DEBUG_NO_UNITS) &&
+                             plan_units(req_off, plan, pl.msg_rep, n, pl.units);
+  sh.smsum = sh.sm && sh.use_units;
+  sh.n_units = sh.use_units ? pl.units.n_units : 0;
+  sh.unit_base = n + C;
+  sh.indiv_vbase = n + C + sh.n_units;
+  sh.n_total = sh.sigagg ? sh.indiv_vbase + R : n;
+  sh.n_prod = sh.sigagg ? sh.indiv_vbase : n;
+  // the chunk groups' sum plan is staged with the inputs
+  if (sh.sigagg && !sh.smsum) plan_gsum(req_off, plan.chunk_off, plan.chunk_reqs, pl.chunk_gsum);
+  if (sh.use_units && !sh.smsum) plan_gsum_sets(pl.units.goff, pl.units.members, pl.unit_gsum);
+  sh.use_total = sh.sigagg && !sh.sm && sh.merged && C > 1 && sig_total_on();
+  sh.use_msm = sh.use_total && n <= MSM_MAX_SETS && ((msm_on() && !sh.merged_after_fail) || (flags & BLS_DEBUG_MSM));
+  if (sh.use_total) {
+    std::vector<uint32_t> goff(C + 1, (uint32_t)pl.chunk_gsum.gsets.size());
+    goff[0] = 0;
+    plan_gsum_sets(goff, pl.chunk_gsum.gsets, pl.total_gsum);
+  }
+  sh.gseg_cap = gseg_cap(n, R);
+  sh.gtmp_cap = gtmp_cap(n, R);
+  sh.ml_shared = sh.sigagg && ml_shared_on();
+  if (sh.ml_shared) plan_ml_domains(req_off, plan, sh.use_units ? &pl.units : nullptr, n, pl.ml_dom);
   if (in->set_pk_offsets)
     for (uint32_t i = 0; i < n; ++i)
-      if (in->set_pk_offsets[i + 1] - in->set_pk_offsets[i] >= BLS_AGG_WAVE_MIN) agg_list.push_back(i);
+      if (in->set_pk_offsets[i + 1] - in->set_pk_offsets[i] >= BLS_AGG_WAVE_MIN) pl.agg_list.push_back(i);
+  sh.fe_min = fe_simt_min();
+  sh.fe_simt_possible = sh.fe_min > 0 && (C >= sh.fe_min || R >= sh.fe_min);
+  sh.gt_min = group_test_min(ctx);
+  for (uint32_t ch = 0; ch < C && !sh.gt_possible; ++ch)
+    sh.gt_possible = plan.chunk_off[ch + 1] - plan.chunk_off[ch] >= sh.gt_min;
+  sh.grp_cap = sh.gt_possible ? grp_cap(R, C) : 0;
+  sh.grp_mem_cap = sh.gt_possible ? grp_mem_cap(R) : 0;
+  sh.gt_eq_mode = group_eq_mode();
+  sh.gsums_min = group_sums_min();
+  sh.init_set_flag = (flags & BLS_DEBUG_FORCE_EXACT) ? 1u : 0u;
+  sh.pack = (flags & BLS_DEBUG_PACK_MASK) >> 8;
+  sh.mlf_pl = (flags & BLS_DEBUG_MLF_PL_MASK) >> 12;
+  sh.pl_forced = (flags & BLS_DEBUG_MLF_PL_MASK) != 0;
+  return sh;
+}
 
-  uint32_t seed_words[8];
-  {
-    uint8_t seed[32];
-    if (in->seed) {
-      memcpy(seed, in->seed, 32);
-    } else if (getrandom(seed, 32, 0) != 32) {
-      snprintf(ctx->err, sizeof(ctx->err), "getrandom failed");
-      return -3;
-    }
-    scalar_words_from_be32(seed, seed_words);
-  }
+// One verify call's pass over the device: shape and plans fixed at construction, buffers
+// carved by stage_inputs, then the stages in the order verify_body calls them.  Every
+// stage returns 0 or the call's error code (ctx->err set).
+struct VerifyPass {
+  bls_gpu_ctx* const ctx;
+  const bls_batch* const in;
+  const PassArgs a;
+  const hipStream_t s;
+  PassPlans pl;
+  const PassShape sh;
+  const BatchPlan& plan;
 
-  // ---- carve the workspace: inputs first (one H2D copy), then intermediates
-  Fp12* ptree[2] = {nullptr, nullptr};  // product-tree levels (partial mode, merged check)
+  // ---- buffers (carve / carve_res)
+  PipeBufs b;
+  GroupBufs g;
+  MsmBufs msm;
+  size_t input_end = 0;                  // [0, input_end) of the carve is the mapped staging area
+  Fp12* ptree[2] = {nullptr, nullptr};   // product-tree levels (partial mode, merged check)
   int32_t* merged_ok = nullptr;          // FE(prod f_i) == 1 of the merged check
   uint32_t* gsets_dev = nullptr;         // group-sum plans (aggregated-signature path)
   uint32_t* gseg_dev = nullptr;
   uint32_t* tseg_dev = nullptr;          // the merged signature sum's plan
   G2J* gtmp[2] = {nullptr, nullptr};
-  uint32_t *unit_rep_dev = nullptr, *ugsets_dev = nullptr, *useg_dev = nullptr;  // Miller-loop units
-  uint32_t* own_sets_dev = nullptr;      // the individually verified sets' own Miller loops + the requests' sums (one launch)
-  // SIMT final exponentiations (kernels/k_fin_simt.hip) for a failing pass's many chunk
-  // checks / requests verified alone: 4 Fp12 per task, carved when a pass could need them
-  const uint32_t fe_min = fe_simt_min();
-  const bool fe_simt_possible = fe_min > 0 && (n_chunks >= fe_min || R >= fe_min);
-  Fp12* fe_save = nullptr;
-  MsmBufs msm;
-  memset(&msm, 0, sizeof(msm));
   G1J* utmp[2] = {nullptr, nullptr};
-  // group tests over failed chunks (passes reuse the buffers): pass A <= 1 + 13 tests per
-  // chunk (chunks of < 8192 requests) of <= 8 m members in all, pass B 2 tests, pass C one
-  // test per request
-  // (carved only when some chunk is large enough to be group-tested, group_test_min)
-  bool gt_possible = false;
-  {
-    const uint32_t gmin = group_test_min(ctx);
-    for (uint32_t ch = 0; ch < n_chunks && !gt_possible; ++ch)
-      gt_possible = plan.chunk_off[ch + 1] - plan.chunk_off[ch] >= gmin;
+  uint32_t *unit_rep_dev = nullptr, *ugsets_dev = nullptr, *useg_dev = nullptr;  // Miller-loop units
+  uint32_t* own_sets_dev = nullptr;  // the individually verified sets' own Miller loops + the requests' sums (one launch)
+  Fp12* fe_save = nullptr;
+
+  // ---- what the stages leave for the later ones
+  bool rs_done;          // the per-set RS = [r] sig (chain CH_RS) exist (ensure_rs)
+  uint32_t pass_pl = 0;  // the first pass's items per k_mlf lane
+  std::vector<int32_t> chunk_ok, merged_status;
+  int32_t merged_verdict = 0;
+  uint32_t flagged = 0;
+  bool merged_pass = false, chunk_fe_kept = false;
+  IndivPlan iv;
+  bool gsums = false;   // group sums: the group tests pair one signature sum per test (group_sums)
+  uint32_t n_sum = 0;   // requests pairing their own signature sum: iv.reqs[0, n_sum)
+  std::vector<int32_t> indiv_verdict;
+  FoldPlan fold;        // outlive the kernels that read them from the staging area
+  GsumPlan indiv_gsum;
+
+  VerifyPass(bls_gpu_ctx* c, const bls_batch* batch, const PassArgs& args)
+      : ctx(c), in(batch), a(args), s(c->stream), sh(plan_pass(c, batch, args, pl)), plan(*pl.plan),
+        rs_done(!sh.use_msm), chunk_ok(sh.n_chunks + 1, 0), merged_status(sh.merged ? sh.R : 0, 0) {
+    memset(&b, 0, sizeof(b));
+    memset(&g, 0, sizeof(g));
+    memset(&msm, 0, sizeof(msm));
   }
-  const size_t grp_cap = gt_possible ? (size_t)R + 14ull * n_chunks + 2 : 0,
-               grp_mem_cap = gt_possible ? 8ull * R + 16 : 0;
-  GroupBufs gbufs;
-  memset(&gbufs, 0, sizeof(gbufs));
-  auto carve = [&](Carver& c, PipeBufs& b, size_t& input_end) {
+
+  // ---- workspace: inputs first (they live in the mapped staging area), then intermediates.
+  // Runs once without a base for the sizes and once for the pointers.
+  void carve(Carver& c) {
+    const uint32_t n = sh.n, R = sh.R, n_chunks = sh.n_chunks;
+    const bool sigagg = sh.sigagg, units = sh.use_units, gt = sh.gt_possible;
     b.req_off = c.take<uint32_t>(R + 1);
     b.chunk_off = c.take<uint32_t>(n_chunks + 1);
     b.chunk_reqs = c.take<uint32_t>(plan.chunk_reqs.size());
     b.seed = c.take<uint32_t>(8);
     b.pubkeys = in->set_pk_offsets ? nullptr : c.take<uint8_t>(96ull * n);
     b.set_pk_off = in->set_pk_offsets ? c.take<uint32_t>(n + 1) : nullptr;
-    b.pk_idx = in->set_pk_offsets ? c.take<uint32_t>(n_pk_idx) : nullptr;
-    b.agg_sets = agg_list.empty() ? nullptr : c.take<uint32_t>(agg_list.size());
+    b.pk_idx = in->set_pk_offsets ? c.take<uint32_t>(sh.n_pk_idx) : nullptr;
+    b.agg_sets = pl.agg_list.empty() ? nullptr : c.take<uint32_t>(pl.agg_list.size());
     b.msgs = c.take<uint8_t>(32ull * n);
-    b.msg_uniq = dedup ? c.take<uint32_t>(n_uniq) : nullptr;
-    b.msg_rep = dedup ? c.take<uint32_t>(n) : nullptr;
+    b.msg_uniq = sh.dedup ? c.take<uint32_t>(sh.n_uniq) : nullptr;
+    b.msg_rep = sh.dedup ? c.take<uint32_t>(n) : nullptr;
     b.sigs = c.take<uint8_t>(96ull * n);
     b.sig_lens = in->signature_lens ? c.take<uint32_t>(n) : nullptr;
     b.indiv_reqs = c.take<uint32_t>(R);
-    gbufs.off = c.take<uint32_t>(gt_possible ? grp_cap + 1 : 0);
-    gbufs.members = c.take<uint32_t>(grp_mem_cap);
-    gbufs.ref = c.take<uint32_t>(gt_possible ? grp_cap : 0);
+    g.off = c.take<uint32_t>(gt ? sh.grp_cap + 1 : 0);
+    g.members = c.take<uint32_t>(sh.grp_mem_cap);
+    g.ref = c.take<uint32_t>(gt ? sh.grp_cap : 0);
     own_sets_dev = sigagg ? c.take<uint32_t>((size_t)n + R) : nullptr;
     b.fold_groups = c.take<uint32_t>(2ull * (n / BLS_FOLD1 + R + 1) + 2ull * (n / BLS_FOLD + R + 1));
-    b.ml_dom = ml_shared ? c.take<uint32_t>(indiv_vbase) : nullptr;
+    b.ml_dom = sh.ml_shared ? c.take<uint32_t>(sh.indiv_vbase) : nullptr;
     gsets_dev = sigagg ? c.take<uint32_t>(n) : nullptr;
-    gseg_dev = sigagg ? c.take<uint32_t>(gseg_cap) : nullptr;
-    tseg_dev = use_total ? c.take<uint32_t>(total_gsum.seg.size()) : nullptr;
-    if (use_units) {
+    gseg_dev = sigagg ? c.take<uint32_t>(sh.gseg_cap) : nullptr;
+    tseg_dev = sh.use_total ? c.take<uint32_t>(pl.total_gsum.seg.size()) : nullptr;
+    if (units) {
       b.set_unit = c.take<uint32_t>(n);
-      unit_rep_dev = c.take<uint32_t>(n_units);
+      unit_rep_dev = c.take<uint32_t>(sh.n_units);
       b.unit_off = c.take<uint32_t>(n_chunks + 1);
-      ugsets_dev = smsum ? nullptr : c.take<uint32_t>(units.members.size());
-      useg_dev = smsum ? nullptr : c.take<uint32_t>(unit_gsum.seg.size());
+      ugsets_dev = sh.smsum ? nullptr : c.take<uint32_t>(pl.units.members.size());
+      useg_dev = sh.smsum ? nullptr : c.take<uint32_t>(pl.unit_gsum.seg.size());
     }
     input_end = c.off;
     b.sig = c.take<G2A>(n);
     b.sig_status = c.take<int32_t>(n);
     b.pk = c.take<G1J>(n);
     b.pk_status = c.take<int32_t>(n);
-    b.pk_inf = partial ? c.take<uint8_t>(n) : nullptr;
+    b.pk_inf = sh.partial ? c.take<uint8_t>(n) : nullptr;
     b.q = c.take<Fp>(8ull * n);
-    b.chain = sigagg ? c.take<Fp>((size_t)CHAIN_WORDS * n_total) : nullptr;
-    b.chain_live = sigagg ? c.take<uint32_t>(n_total) : nullptr;
+    b.chain = sigagg ? c.take<Fp>((size_t)CHAIN_WORDS * sh.n_total) : nullptr;
+    b.chain_live = sigagg ? c.take<uint32_t>(sh.n_total) : nullptr;
     b.chain_st = sigagg ? c.take<uint8_t>(4ull * n) : nullptr;
     b.rtab2 = sigagg ? c.take<G2J>(15ull * n) : nullptr;
     b.rtab1 = c.take<G1J>((sigagg ? 15ull : 30ull) * n);
     b.rpts = sigagg ? nullptr : c.take<G1J>(2ull * n);
-    gtmp[0] = sigagg ? c.take<G2J>(gtmp_cap) : nullptr;
-    gtmp[1] = sigagg ? c.take<G2J>(gtmp_cap) : nullptr;
-    utmp[0] = use_units && !smsum ? c.take<G1J>(unit_gsum.level_off[1] + 1) : nullptr;
-    utmp[1] = use_units && !smsum ? c.take<G1J>(unit_gsum.level_off[1] + 1) : nullptr;
+    gtmp[0] = sigagg ? c.take<G2J>(sh.gtmp_cap) : nullptr;
+    gtmp[1] = sigagg ? c.take<G2J>(sh.gtmp_cap) : nullptr;
+    utmp[0] = units && !sh.smsum ? c.take<G1J>(pl.unit_gsum.level_off[1] + 1) : nullptr;
+    utmp[1] = units && !sh.smsum ? c.take<G1J>(pl.unit_gsum.level_off[1] + 1) : nullptr;
     b.set_flag = c.take<uint32_t>(n);
     b.flag_count = c.take<uint32_t>(1);
-    b.f = c.take<Fp12>(n_total);
-    b.ml_lines = sigagg ? c.take<uint32_t>(mlq_line_words(n_total)) : nullptr;
-    if (use_msm) {
+    b.f = c.take<Fp12>(sh.n_total);
+    b.ml_lines = sigagg ? c.take<uint32_t>(mlq_line_words(sh.n_total)) : nullptr;
+    if (sh.use_msm) {
       msm.off = c.take<uint32_t>(MSM_BUCKETS + 1);
       msm.seg_off = c.take<uint32_t>(MSM_BUCKETS + 1);
       msm.ent = c.take<uint32_t>(8ull * n);
@@ -1469,298 +1179,347 @@ static int verify_body(bls_gpu_ctx* ctx, const bls_batch* in, int32_t* verdicts,
       msm.win = c.take<G2J>(4);
     }
     b.req_status = c.take<int32_t>(R);
-    gbufs.f = gt_possible ? c.take<Fp12>(R) : nullptr;
-    gbufs.fe = gt_possible ? c.take<Fp12>(grp_cap) : nullptr;
-    b.chunk_fe = gt_possible ? c.take<Fp12>(n_chunks) : nullptr;
-    fe_save = fe_simt_possible ? c.take<Fp12>(4ull * (n_chunks > R ? n_chunks : R)) : nullptr;
-    if (partial || merged) {
-      ptree[0] = c.take<Fp12>((n_total + FPROD_FAN - 1) / FPROD_FAN);
-      ptree[1] = c.take<Fp12>((n_total + FPROD_FAN - 1) / FPROD_FAN);
+    g.f = gt ? c.take<Fp12>(R) : nullptr;
+    g.fe = gt ? c.take<Fp12>(sh.grp_cap) : nullptr;
+    b.chunk_fe = gt ? c.take<Fp12>(n_chunks) : nullptr;
+    fe_save = sh.fe_simt_possible ? c.take<Fp12>(4ull * (n_chunks > R ? n_chunks : R)) : nullptr;
+    if (sh.partial || sh.merged) {
+      ptree[0] = c.take<Fp12>((sh.n_total + FPROD_FAN - 1) / FPROD_FAN);
+      ptree[1] = c.take<Fp12>((sh.n_total + FPROD_FAN - 1) / FPROD_FAN);
     }
-  };
+  }
   // results: written by the kernels straight into host-mapped memory
-  auto carve_res = [&](Carver& c, PipeBufs& b) {
-    b.chunk_ok = c.take<int32_t>(n_chunks);
-    b.indiv_verdict = c.take<int32_t>(R);
-    gbufs.verdict = c.take<int32_t>(grp_cap);
-    b.req_status_host = c.take<int32_t>(R);
+  void carve_res(Carver& c) {
+    b.chunk_ok = c.take<int32_t>(sh.n_chunks);
+    b.indiv_verdict = c.take<int32_t>(sh.R);
+    g.verdict = c.take<int32_t>(sh.grp_cap);
+    b.req_status_host = c.take<int32_t>(sh.R);
     b.flag_count_host = c.take<uint32_t>(1);
-    merged_ok = merged ? c.take<int32_t>(1) : nullptr;
-  };
-  PipeBufs b;
-  memset(&b, 0, sizeof(b));
-  size_t input_end = 0;
-  {
-    Carver c{nullptr, 0}, cr{nullptr, 0};
-    carve(c, b, input_end);
-    carve_res(cr, b);
-    if (ensure_dev(ctx, c.off) || ensure_host(ctx, input_end) ||
-        ensure_mapped(ctx, cr.off, &ctx->host_res, &ctx->host_res_dev, &ctx->host_res_cap))
-      return -1;
-  }
-  // inputs [0, input_end) live in the mapped staging area, the rest in device memory
-  Carver c{ctx->dev_ws, 0, ctx->host_stage_dev, input_end};
-  carve(c, b, input_end);
-  Carver cr{ctx->host_res_dev, 0};
-  carve_res(cr, b);
-  b.first_bad_pk = b.pubkeys ? ctx->first_bad + ctx->first_bad_slot : nullptr;
-  b.first_bad_pk_next = ctx->first_bad + (ctx->first_bad_slot ^ 1u);
-  b.init_set_flag = (ctx->debug_flags & BLS_DEBUG_FORCE_EXACT) ? 1u : 0u;
-  b.n_sets = n;
-  b.n_reqs = R;
-  b.n_chunks = n_chunks;
-  b.pk_table = ctx->table;
-  b.pk_table_n = ctx->table_n;
-  b.scalar_base = scalar_base;
-  b.pack = (ctx->debug_flags & BLS_DEBUG_PACK_MASK) >> 8;
-  b.mlf_pl = (ctx->debug_flags & BLS_DEBUG_MLF_PL_MASK) >> 12;
-  b.multi_set_rules = partial ? 1u : 0u;
-  b.sigagg = sigagg ? 1u : 0u;
-  b.unit_base = unit_base;
-  b.n_units = n_units;
-  b.indiv_vbase = indiv_vbase;
-  if (use_units) {
-    stage_copy(ctx, b.set_unit, units.set_unit.data(), sizeof(uint32_t) * n);
-    stage_copy(ctx, unit_rep_dev, units.unit_rep.data(), sizeof(uint32_t) * n_units);
-    stage_copy(ctx, b.unit_off, units.unit_off.data(), sizeof(uint32_t) * (n_chunks + 1));
-    if (!smsum) {
-      stage_copy(ctx, ugsets_dev, units.members.data(), sizeof(uint32_t) * units.members.size());
-      stage_copy(ctx, useg_dev, unit_gsum.seg.data(), sizeof(uint32_t) * unit_gsum.seg.size());
-    }
-  }
-  if (ml_shared) stage_copy(ctx, b.ml_dom, ml_dom.data(), sizeof(uint32_t) * ml_dom.size());
-  if (sigagg) {
-    stage_copy(ctx, gsets_dev, chunk_gsum.gsets.data(), sizeof(uint32_t) * chunk_gsum.gsets.size());
-    stage_copy(ctx, gseg_dev, chunk_gsum.seg.data(), sizeof(uint32_t) * chunk_gsum.seg.size());
-    if (use_total) stage_copy(ctx, tseg_dev, total_gsum.seg.data(), sizeof(uint32_t) * total_gsum.seg.size());
+    merged_ok = sh.merged ? c.take<int32_t>(1) : nullptr;
   }
 
-  stage_copy(ctx, b.req_off, in->req_set_offsets, sizeof(uint32_t) * (R + 1));
-  stage_copy(ctx, b.chunk_off, plan.chunk_off.data(), sizeof(uint32_t) * (n_chunks + 1));
-  stage_copy(ctx, b.chunk_reqs, plan.chunk_reqs.data(), sizeof(uint32_t) * plan.chunk_reqs.size());
-  stage_copy(ctx, b.seed, seed_words, sizeof(seed_words));
-  if (b.pubkeys) stage_copy(ctx, b.pubkeys, in->pubkeys, 96ull * n);
-  if (b.set_pk_off) {
-    stage_copy(ctx, b.set_pk_off, in->set_pk_offsets, sizeof(uint32_t) * (n + 1));
-    stage_copy(ctx, b.pk_idx, in->pk_indices, sizeof(uint32_t) * n_pk_idx);
-  }
-  b.n_agg = (uint32_t)agg_list.size();
-  b.agg_min = agg_list.empty() ? 0u : BLS_AGG_WAVE_MIN;
-  if (!agg_list.empty()) stage_copy(ctx, b.agg_sets, agg_list.data(), sizeof(uint32_t) * agg_list.size());
-  stage_copy(ctx, b.msgs, in->messages, 32ull * n);
-  b.n_uniq = dedup ? n_uniq : 0;
-  if (dedup) {
-    stage_copy(ctx, b.msg_uniq, msg_uniq.data(), sizeof(uint32_t) * n_uniq);
-    stage_copy(ctx, b.msg_rep, msg_rep.data(), sizeof(uint32_t) * n);
-  }
-  if (in->signature_lens) {
-    // bytes past a short signature's length are never read (the set fails INVALID_SIZE)
-    for (uint32_t i = 0; i < n; ++i) {
-      uint32_t len = in->signature_lens[i] < 96 ? in->signature_lens[i] : 96;
-      uint8_t* dst = ctx->host_stage + ((const uint8_t*)b.sigs - ctx->host_stage_dev) + 96ull * i;
-      memset(dst, 0, 96);
-      memcpy(dst, in->signatures + 96ull * i, len);
-    }
-    stage_copy(ctx, b.sig_lens, in->signature_lens, sizeof(uint32_t) * n);
-  } else {
-    stage_copy(ctx, b.sigs, in->signatures, 96ull * n);
+  // the fields of b that are no pointers into the carve
+  void fill_fields() {
+    b.first_bad_pk = b.pubkeys ? ctx->first_bad + ctx->first_bad_slot : nullptr;
+    b.first_bad_pk_next = ctx->first_bad + (ctx->first_bad_slot ^ 1u);
+    b.init_set_flag = sh.init_set_flag;
+    b.n_sets = sh.n;
+    b.n_reqs = sh.R;
+    b.n_chunks = sh.n_chunks;
+    b.pk_table = ctx->table;
+    b.pk_table_n = ctx->table_n;
+    b.scalar_base = a.scalar_base;
+    b.pack = sh.pack;
+    b.mlf_pl = sh.mlf_pl;
+    b.multi_set_rules = sh.partial ? 1u : 0u;
+    b.sigagg = sh.sigagg ? 1u : 0u;
+    b.unit_base = sh.unit_base;
+    b.n_units = sh.n_units;
+    b.indiv_vbase = sh.indiv_vbase;
+    b.n_agg = (uint32_t)pl.agg_list.size();
+    b.agg_min = pl.agg_list.empty() ? 0u : BLS_AGG_WAVE_MIN;
+    b.n_uniq = sh.dedup ? sh.n_uniq : 0;
   }
 
-  hipStream_t s = ctx->stream;
-  HIPC(ctx, hipEventRecord(ctx->ev0, s));
-  HIPC(ctx, hipEventRecord(ctx->ev[0], s));  // no H2D stage: the kernels read the mapped inputs
-  if (n > 0) {
+  template <class T>
+  void stage_vec(const T* dev_ptr, const std::vector<T>& v) {
+    stage_copy(ctx, dev_ptr, v.data(), sizeof(T) * v.size());
+  }
+
+  void copy_plans() {
+    if (sh.use_units) {
+      stage_vec(b.set_unit, pl.units.set_unit);
+      stage_vec(unit_rep_dev, pl.units.unit_rep);
+      stage_vec(b.unit_off, pl.units.unit_off);
+      if (!sh.smsum) {
+        stage_vec(ugsets_dev, pl.units.members);
+        stage_vec(useg_dev, pl.unit_gsum.seg);
+      }
+    }
+    if (sh.ml_shared) stage_vec(b.ml_dom, pl.ml_dom);
+    if (sh.sigagg) {
+      stage_vec(gsets_dev, pl.chunk_gsum.gsets);
+      stage_vec(gseg_dev, pl.chunk_gsum.seg);
+      if (sh.use_total) stage_vec(tseg_dev, pl.total_gsum.seg);
+    }
+    stage_vec(b.chunk_off, plan.chunk_off);
+    stage_vec(b.chunk_reqs, plan.chunk_reqs);
+    if (!pl.agg_list.empty()) stage_vec(b.agg_sets, pl.agg_list);
+    if (sh.dedup) {
+      stage_vec(b.msg_uniq, pl.msg_uniq);
+      stage_vec(b.msg_rep, pl.msg_rep);
+    }
+  }
+
+  void copy_inputs(const uint32_t seed_words[8]) {
+    const uint32_t n = sh.n;
+    stage_copy(ctx, b.req_off, in->req_set_offsets, sizeof(uint32_t) * (sh.R + 1));
+    stage_copy(ctx, b.seed, seed_words, sizeof(uint32_t) * 8);
+    if (b.pubkeys) stage_copy(ctx, b.pubkeys, in->pubkeys, 96ull * n);
+    if (b.set_pk_off) {
+      stage_copy(ctx, b.set_pk_off, in->set_pk_offsets, sizeof(uint32_t) * (n + 1));
+      stage_copy(ctx, b.pk_idx, in->pk_indices, sizeof(uint32_t) * sh.n_pk_idx);
+    }
+    stage_copy(ctx, b.msgs, in->messages, 32ull * n);
+    if (in->signature_lens) {
+      // bytes past a short signature's length are never read (the set fails INVALID_SIZE)
+      for (uint32_t i = 0; i < n; ++i) {
+        uint32_t len = in->signature_lens[i] < 96 ? in->signature_lens[i] : 96;
+        uint8_t* dst = ctx->host_stage + ((const uint8_t*)b.sigs - ctx->host_stage_dev) + 96ull * i;
+        memset(dst, 0, 96);
+        memcpy(dst, in->signatures + 96ull * i, len);
+      }
+      stage_copy(ctx, b.sig_lens, in->signature_lens, sizeof(uint32_t) * n);
+    } else {
+      stage_copy(ctx, b.sigs, in->signatures, 96ull * n);
+    }
+  }
+
+  // a group-sum plan must fit the workspace every pass keeps for one (bls/plan.hpp gsum_fits)
+  int check_gsum(const GsumPlan& p) {
+    if (gsum_fits(p, sh.n, sh.R)) return 0;
+    snprintf(ctx->err, sizeof(ctx->err), "group-sum plan exceeds its workspace");
+    return -3;
+  }
+
+  // ---- stage: seed, workspace, plans and inputs into the staging area
+  int stage_inputs() {
+    if (sh.sigagg)
+      if (const int rc = check_gsum(pl.chunk_gsum)) return rc;
+    uint32_t seed_words[8];
+    uint8_t seed[32];
+    if (in->seed) {
+      memcpy(seed, in->seed, 32);
+    } else if (getrandom(seed, 32, 0) != 32) {
+      snprintf(ctx->err, sizeof(ctx->err), "getrandom failed");
+      return -3;
+    }
+    scalar_words_from_be32(seed, seed_words);
+    {
+      Carver c{nullptr, 0}, cr{nullptr, 0};
+      carve(c);
+      carve_res(cr);
+      if (ensure_dev(ctx, c.off) || ensure_host(ctx, input_end) ||
+          ensure_mapped(ctx, cr.off, &ctx->host_res, &ctx->host_res_dev, &ctx->host_res_cap))
+        return -1;
+    }
+    Carver c{ctx->dev_ws, 0, ctx->host_stage_dev, input_end};
+    carve(c);
+    Carver cr{ctx->host_res_dev, 0};
+    carve_res(cr);
+    fill_fields();
+    copy_plans();
+    copy_inputs(seed_words);
+    return 0;
+  }
+
+  // the levels of a G2 group-sum plan and k_vset for its groups -> virtual sets vbase + g
+  int launch_gsum(const GsumPlan& p, const uint32_t* seg_dev, uint32_t vbase) {
+    b.gsets = gsets_dev;
+    const G2J* sums = nullptr;
+    if (gsum_levels(ctx, b, p, seg_dev, gtmp, "k_gsum", &sums, s)) return -1;
+    const size_t levels = p.level_off.size() - 1;
+    const uint32_t G = levels ? p.level_off[levels] - p.level_off[levels - 1] : 0;
+    HIPC(ctx, launch_k_vset(b, sums, G, vbase, s)); dbg_sync(s, "k_vset");
+    return 0;
+  }
+
+  // ---- stage: the first pass.  stage_ms[1] k_pk, [2] k_pre, [3] k_chain (or k_pset), [4]
+  // the signature sums (k_gsum / k_msm / k_smsum, units), [5] the Miller loops (k_mln; the
+  // per-set path has none of its own): the per-kernel launch times bench.py prices
+  int first_pass() {
+    HIPC(ctx, hipEventRecord(ctx->ev0, s));
+    HIPC(ctx, hipEventRecord(ctx->ev[0], s));  // no H2D stage: the kernels read the mapped inputs
+    if (sh.n == 0) {
+      for (int i = 1; i <= 5; ++i) HIPC(ctx, hipEventRecord(ctx->ev[i], s));
+      return 0;
+    }
     HIPC(ctx, launch_k_pk(b, s));  // also resets set_flag, flag_count, the next first_bad_pk slot
     HIPC(ctx, launch_k_pk_agg(b, s)); dbg_sync(s, "k_pk");
     ctx->first_bad_slot ^= 1u;
     HIPC(ctx, hipEventRecord(ctx->ev[1], s));
     HIPC(ctx, launch_k_pre(b, s)); dbg_sync(s, "k_pre");
     HIPC(ctx, hipEventRecord(ctx->ev[2], s));
-    if (sigagg) {
-      // per-set chains, the chunks' sums of r sig -> virtual sets n + c, then every
-      // Miller loop (sets and virtual sets) in one launch
-      HIPC(ctx, launch_k_chain(b, s, use_msm ? 0xBu : 0xFu)); dbg_sync(s, "k_chain");
-      HIPC(ctx, hipEventRecord(ctx->ev[3], s));
-      if (smsum) {
-        // each job's two pairing inputs in one step (kernels/k_smsg.hip)
-        HIPC(ctx, launch_k_smsum(b, unit_rep_dev, s)); dbg_sync(s, "k_smsum");
-      } else if (use_msm) {
-        msm.cnt = ctx->msm_state;
-        msm.ticket = ctx->msm_state + MSM_BUCKETS;
-        HIPC(ctx, launch_k_msm(b, msm, n_chunks, n, s)); dbg_sync(s, "k_msm");
-      } else if (launch_gsum(ctx, b, use_total ? total_gsum : chunk_gsum, use_total ? tseg_dev : gseg_dev, gsets_dev,
-                             gtmp, n, s)) {
-        return -1;
-      }
-      if (use_units && !smsum) {
-        // sum r_i pk_i per unit (levels over the members), then the units' chain entries
-        b.gsets = ugsets_dev;
-        const G1J* uin = nullptr;
-        const size_t levels = unit_gsum.level_off.size() - 1;
-        for (size_t L = 0; L < levels; ++L) {
-          const uint32_t beg = unit_gsum.level_off[L], n_seg = unit_gsum.level_off[L + 1] - beg;
-          HIPC(ctx, launch_k_gsum1(b, useg_dev + 2 * beg, n_seg, uin, utmp[L & 1], s)); dbg_sync(s, "k_gsum1");
-          uin = utmp[L & 1];
-        }
-        HIPC(ctx, launch_k_uset(b, uin, unit_rep_dev, s)); dbg_sync(s, "k_uset");
-        b.gsets = gsets_dev;
-      }
-      HIPC(ctx, hipEventRecord(ctx->ev[4], s));
-      // the f-side shape is chosen once per call (other contexts change the sets in flight
-      // meanwhile): the first pass's Miller-loop launch and stats->pass_shape use it
-      if (!b.mlf_pl && k_mln_list_ok(b)) b.mlf_pl = mlf_per_lane();
-      // a same-message call's first pass has two Miller loops per job (its unit and its
-      // signature sum) and one per 1-set job: few items that never share f, so they run as
-      // the cooperative single-pair loops, one wavefront each (launch_k_mln_coop: ~1 ms
-      // where the SIMT pair takes ~7 ms), while they fit coop_ml_max()
-      hipError_t ml_rc = hipErrorNotSupported;
-      if (sm && k_mln_list_ok(b) && !(ctx->debug_flags & BLS_DEBUG_MLF_PL_MASK)) {
-        std::vector<uint32_t> items(plan.nonbatch_reqs);
-        for (uint32_t ch = 0; ch < n_chunks; ++ch) items.push_back(n + ch);
-        for (uint32_t u = 0; u < n_units; ++u) items.push_back(unit_base + u);
-        if (items.size() <= coop_ml_max()) {
-          stage_copy(ctx, own_sets_dev, items.data(), sizeof(uint32_t) * items.size());
-          ml_rc = launch_k_mln_coop(b, ctx->coop, 0, (uint32_t)items.size(), own_sets_dev, s);
-        }
-      }
-      if (ml_rc == hipErrorNotSupported) ml_rc = launch_k_mln(b, ctx->coop, 0, indiv_vbase, s);
-      HIPC(ctx, ml_rc); dbg_sync(s, "k_mln");
+    if (sh.sigagg) {
+      if (first_pass_aggregated()) return -1;
     } else {
       HIPC(ctx, launch_k_pset(b, ctx->coop, s)); dbg_sync(s, "k_pset");
       HIPC(ctx, hipEventRecord(ctx->ev[3], s));
       HIPC(ctx, hipEventRecord(ctx->ev[4], s));
     }
-    // stage_ms[3] k_chain (or k_pset), [4] the signature sums (k_gsum / k_msm, units),
-    // [5] the Miller loops (k_mlq + k_mlf): the per-kernel launch times bench.py prices
     HIPC(ctx, hipEventRecord(ctx->ev[5], s));
-  } else {
-    for (int i = 1; i <= 5; ++i) HIPC(ctx, hipEventRecord(ctx->ev[i], s));
+    return 0;
   }
-  HIPC(ctx, launch_k_status(b, s)); dbg_sync(s, "k_status");
+
+  // per-set chains, the chunks' sums of r sig -> virtual sets n + c, the units' sums, then
+  // every Miller loop (sets and virtual sets) in one launch
+  int first_pass_aggregated() {
+    HIPC(ctx, launch_k_chain(b, s, sh.use_msm ? 0xBu : 0xFu)); dbg_sync(s, "k_chain");
+    HIPC(ctx, hipEventRecord(ctx->ev[3], s));
+    if (sh.smsum) {
+      // each job's two pairing inputs in one step (kernels/k_smsg.hip)
+      HIPC(ctx, launch_k_smsum(b, unit_rep_dev, s)); dbg_sync(s, "k_smsum");
+    } else if (sh.use_msm) {
+      msm.cnt = ctx->msm_state;
+      msm.ticket = ctx->msm_state + MSM_BUCKETS;
+      HIPC(ctx, launch_k_msm(b, msm, sh.n_chunks, sh.n, s)); dbg_sync(s, "k_msm");
+    } else if (sh.use_total ? launch_gsum(pl.total_gsum, tseg_dev, sh.n) : launch_gsum(pl.chunk_gsum, gseg_dev, sh.n)) {
+      return -1;
+    }
+    if (sh.use_units && !sh.smsum) {
+      // sum r_i pk_i per unit (levels over the members), then the units' chain entries
+      b.gsets = ugsets_dev;
+      const G1J* usums = nullptr;
+      if (gsum_levels(ctx, b, pl.unit_gsum, useg_dev, utmp, "k_gsum1", &usums, s)) return -1;
+      HIPC(ctx, launch_k_uset(b, usums, unit_rep_dev, s)); dbg_sync(s, "k_uset");
+      b.gsets = gsets_dev;
+    }
+    HIPC(ctx, hipEventRecord(ctx->ev[4], s));
+    // the f-side shape is chosen once per call (other contexts change the sets in flight
+    // meanwhile): the first pass's Miller-loop launch and stats->pass_shape use it
+    if (!b.mlf_pl && k_mln_list_ok(b)) b.mlf_pl = mlf_per_lane();
+    // a same-message call's first pass has two Miller loops per job (its unit and its
+    // signature sum) and one per 1-set job: few items that never share f, so they run as
+    // the cooperative single-pair loops, one wavefront each (launch_k_mln_coop: ~1 ms
+    // where the SIMT pair takes ~7 ms), while they fit coop_ml_max()
+    hipError_t ml_rc = hipErrorNotSupported;
+    if (sh.sm && k_mln_list_ok(b) && !sh.pl_forced) {
+      std::vector<uint32_t> items(plan.nonbatch_reqs);
+      for (uint32_t ch = 0; ch < sh.n_chunks; ++ch) items.push_back(sh.n + ch);
+      for (uint32_t u = 0; u < sh.n_units; ++u) items.push_back(sh.unit_base + u);
+      if (items.size() <= coop_ml_max()) {
+        stage_vec(own_sets_dev, items);
+        ml_rc = launch_k_mln_coop(b, ctx->coop, 0, (uint32_t)items.size(), own_sets_dev, s);
+      }
+    }
+    if (ml_rc == hipErrorNotSupported) ml_rc = launch_k_mln(b, ctx->coop, 0, sh.indiv_vbase, s);
+    HIPC(ctx, ml_rc); dbg_sync(s, "k_mln");
+    return 0;
+  }
+
   // Merged check: FE(prod of every f_i) == 1 with one final exponentiation (k_fprod
   // tree 1024 -> 16 -> 1), before any per-chunk one.
-  const uint32_t n_prod = sigagg ? indiv_vbase : n;  // the f's of every set, chunk group and unit
-  auto launch_merged = [&]() -> int {
-    const Fp12* cur = b.f;
-    uint32_t m = n_prod, lvl = 0;
-    while (m > FPROD_FAN) {
-      HIPC(ctx, launch_k_fprod(cur, m, ptree[lvl & 1], nullptr, ctx->coop, s)); dbg_sync(s, "k_fprod");
-      cur = ptree[lvl & 1];
-      m = (m + FPROD_FAN - 1) / FPROD_FAN;
-      ++lvl;
-    }
-    HIPC(ctx, launch_k_fprod(cur, m, nullptr, merged_ok, ctx->coop, s)); dbg_sync(s, "k_fprod merged");
-    return 0;
-  };
-  if (merged && launch_merged()) return -1;
-  HIPC(ctx, hipEventRecord(ctx->ev[6], s));
+  int launch_merged() { return fprod_tree(ctx, b.f, sh.n_prod, ptree, merged_ok, nullptr, s); }
 
-  // the per-set RS = [r] sig (chain CH_RS) the fallback sums need: made by the first pass
-  // unless the MSM replaced role 2 there
-  bool rs_done = !use_msm;
-  auto ensure_rs = [&]() -> int {
+  // after a stream sync: the merged verdict and the statuses, from the mapped result area
+  void read_merged() {
+    merged_verdict = *res_host(ctx, merged_ok);
+    memcpy(merged_status.data(), res_host(ctx, b.req_status_host), sizeof(int32_t) * sh.R);
+  }
+
+  // ---- stage: statuses and the merged check, then the pass's first wait.  stage_ms[6]
+  int merged_check() {
+    pass_pl = b.mlf_pl;
+    HIPC(ctx, launch_k_status(b, s)); dbg_sync(s, "k_status");
+    if (sh.merged && launch_merged()) return -1;
+    HIPC(ctx, hipEventRecord(ctx->ev[6], s));
+    HIPC(ctx, pass_wait(ctx, s));
+    if (sh.merged) read_merged();
+    if (sh.n > 0) flagged = *res_host(ctx, b.flag_count_host);
+    return 0;
+  }
+
+  // ---- stage (rare): sets the cooperative kernel could not finish (exceptional additions,
+  // infinity signatures, special SSWU inputs) -> exact path, then the status (the exact
+  // path may find a signature outside G2) and the merged check again
+  int flagged_redo() {
+    if (!flagged) return 0;
+    HIPC(ctx, launch_k_exact(b, s)); dbg_sync(s, "k_exact");
+    HIPC(ctx, launch_k_status(b, s)); dbg_sync(s, "k_status");
+    if (sh.merged && launch_merged()) return -1;
+    HIPC(ctx, pass_wait(ctx, s));
+    if (sh.merged) read_merged();
+    return 0;
+  }
+
+  // the per-set RS the fallback sums need: made by the first pass unless the MSM replaced
+  // role 2 there
+  int ensure_rs() {
     if (!rs_done) {
       HIPC(ctx, launch_k_chain(b, s, 0x4u)); dbg_sync(s, "k_chain rs");
       rs_done = true;
     }
     return 0;
-  };
+  }
   // the Miller-loop launches after the first pass take their own items-per-lane
   // (mlf_per_lane_alone: their items never share f) unless a test forces one
-  const uint32_t pass_pl = b.mlf_pl;
-  const bool pl_forced = (ctx->debug_flags & BLS_DEBUG_MLF_PL_MASK) != 0;
-  auto alone_pl = [&](uint32_t count) {
-    const uint32_t pl = mlf_per_lane_alone(count);
-    if (pl && !pl_forced && k_mln_list_ok(b)) b.mlf_pl = pl;
-  };
+  void alone_pl(uint32_t count) {
+    const uint32_t pl_alone = mlf_per_lane_alone(count);
+    if (pl_alone && !sh.pl_forced && k_mln_list_ok(b)) b.mlf_pl = pl_alone;
+  }
   // ... and up to coop_ml_max() items they are cooperative single-pair loops, one
   // wavefront per item (launch_k_mln_coop), else the SIMT pair at that shape
-  auto launch_ml_alone = [&](uint32_t first, uint32_t count, const uint32_t* items) -> hipError_t {
+  hipError_t launch_ml_alone(uint32_t first, uint32_t count, const uint32_t* items) {
     if (count == 0) return hipSuccess;
-    if (!pl_forced && k_mln_list_ok(b)) {
+    if (!sh.pl_forced && k_mln_list_ok(b)) {
       const hipError_t e = launch_k_mln_coop(b, ctx->coop, first, count, items, s);
       if (e != hipErrorNotSupported) return e;
     }
     alone_pl(count);
     return items ? launch_k_mln_list(b, items, count, s) : launch_k_mln(b, ctx->coop, first, count, s);
-  };
-  std::vector<int32_t> chunk_ok(n_chunks + 1, 0);
-  std::vector<int32_t> merged_status(merged ? R : 0, 0);
-  int32_t merged_verdict = 0;
-  uint32_t flagged = 0;
-  // after a stream sync: the merged verdict and the statuses, from the mapped result area
-  auto read_merged = [&]() {
-    merged_verdict = *res_host(ctx, merged_ok);
-    memcpy(merged_status.data(), res_host(ctx, b.req_status_host), sizeof(int32_t) * R);
-  };
-  HIPC(ctx, pass_wait(ctx, s));
-  if (merged) read_merged();
-  if (n > 0) flagged = *res_host(ctx, b.flag_count_host);
-  if (flagged) {
-    // rare: sets the cooperative kernel could not finish (exceptional additions,
-    // infinity signatures, special SSWU inputs) -> exact path, then the status (the
-    // exact path may find a signature outside G2) and the merged check again
-    HIPC(ctx, launch_k_exact(b, s)); dbg_sync(s, "k_exact");
-    HIPC(ctx, launch_k_status(b, s)); dbg_sync(s, "k_status");
-    if (merged && launch_merged()) return -1;
-    HIPC(ctx, pass_wait(ctx, s));
-    if (merged) read_merged();
   }
-  bool merged_pass = merged && merged_verdict == 1;
-  bool chunk_fe_kept = false;
-  for (uint32_t r = 0; merged_pass && r < R; ++r) merged_pass = merged_status[r] == BLS_OK;
-  if (merged && !sm) ctx->last_merged_failed = !merged_pass;
-  if (merged_pass) {
-    for (uint32_t ch = 0; ch < n_chunks; ++ch) chunk_ok[ch] = 1;
-  } else if (n_chunks > 0 && !partial) {
-    // some set is invalid or erroneous (or no merged check): the per-chunk verdicts decide
-    if (ensure_rs()) return -1;
-    if (use_total) {
-      // the chunks' own signature sums and their Miller loops (virtual sets n + c)
-      if (launch_gsum(ctx, b, chunk_gsum, gseg_dev, gsets_dev, gtmp, n, s)) return -1;
-      HIPC(ctx, launch_ml_alone(n, n_chunks, nullptr)); dbg_sync(s, "k_mln chunk sums");
+
+  // ---- stage: the chunk verdicts -- all 1 after a passing merged check, else (not in
+  // partial mode) the per-chunk final exponentiations -- and the stats of the pass so far
+  int chunk_checks() {
+    const uint32_t n_chunks = sh.n_chunks;
+    merged_pass = sh.merged && merged_verdict == 1;
+    for (uint32_t r = 0; merged_pass && r < sh.R; ++r) merged_pass = merged_status[r] == BLS_OK;
+    if (sh.merged && !sh.sm) ctx->last_merged_failed = !merged_pass;
+    if (merged_pass) {
+      for (uint32_t ch = 0; ch < n_chunks; ++ch) chunk_ok[ch] = 1;
+    } else if (n_chunks > 0 && !sh.partial) {
+      // some set is invalid or erroneous (or no merged check): the per-chunk verdicts decide
+      if (ensure_rs()) return -1;
+      if (sh.use_total) {
+        // the chunks' own signature sums and their Miller loops (virtual sets n + c)
+        if (launch_gsum(pl.chunk_gsum, gseg_dev, sh.n)) return -1;
+        HIPC(ctx, launch_ml_alone(sh.n, n_chunks, nullptr)); dbg_sync(s, "k_mln chunk sums");
+      }
+      // many chunk checks: one lane each (a failing pass at the plateau has hundreds, and a
+      // cooperative task holds a SIMD for a whole final exponentiation); few: one wavefront
+      // each, the shorter latency
+      if (fe_save && n_chunks >= sh.fe_min) HIPC(ctx, launch_k_chunk_simt(b, fe_save, s));
+      else {
+        HIPC(ctx, launch_k_chunk_coop(b, ctx->coop, s));
+        chunk_fe_kept = b.chunk_fe != nullptr;  // the checked chunks' final exponentiations
+      }
+      dbg_sync(s, "k_chunk");
+      HIPC(ctx, pass_wait(ctx, s));
+      memcpy(chunk_ok.data(), res_host(ctx, b.chunk_ok), sizeof(int32_t) * n_chunks);
     }
-    // many chunk checks: one lane each (a failing pass at the plateau has hundreds, and a
-    // cooperative task holds a SIMD for a whole final exponentiation); few: one wavefront
-    // each, the shorter latency
-    if (fe_save && n_chunks >= fe_min) HIPC(ctx, launch_k_chunk_simt(b, fe_save, s));
-    else {
-      HIPC(ctx, launch_k_chunk_coop(b, ctx->coop, s));
-      chunk_fe_kept = b.chunk_fe != nullptr;  // the checked chunks' final exponentiations
+    if (sh.merged_skipped) {
+      // the context keeps skipping the merged check while its passes keep failing a chunk
+      bool all_ok = true;
+      for (uint32_t ch = 0; ch < n_chunks; ++ch) all_ok = all_ok && chunk_ok[ch] == 1;
+      ctx->last_merged_failed = !all_ok;
     }
-    dbg_sync(s, "k_chunk");
-    HIPC(ctx, pass_wait(ctx, s));
-    memcpy(chunk_ok.data(), res_host(ctx, b.chunk_ok), sizeof(int32_t) * n_chunks);
+    if (a.stats) {
+      a.stats->merged_check = sh.merged ? (merged_pass ? 1 : 2) : (sh.merged_skipped ? 3 : 0);
+      a.stats->pass_shape = sh.sigagg ? ((sh.use_msm ? 1u : 0u) | (k_mln_list_ok(b) ? pass_pl << 8 : 0u)) : 0u;
+      a.stats->n_flagged = flagged;
+      a.stats->n_unique_msgs = sh.n_uniq;
+      a.stats->n_ml_units = sh.n_units;
+    }
+    return 0;
   }
-  if (merged_skipped) {
-    // the context keeps skipping the merged check while its passes keep failing a chunk
-    bool all_ok = true;
-    for (uint32_t ch = 0; ch < n_chunks; ++ch) all_ok = all_ok && chunk_ok[ch] == 1;
-    ctx->last_merged_failed = !all_ok;
-  }
-  if (stats) {
-    stats->merged_check = merged ? (merged_pass ? 1 : 2) : (merged_skipped ? 3 : 0);
-    stats->pass_shape =
-        sigagg ? ((use_msm ? 1u : 0u) | (k_mln_list_ok(b) ? pass_pl << 8 : 0u)) : 0u;
-  }
-  if (stats) {
-    stats->n_flagged = flagged;
-    stats->n_unique_msgs = n_uniq;
-    stats->n_ml_units = n_units;
-  }
-  if (partial) {
-    // the call rejects with the code of its first error, classes in the reference's
-    // order: a pubkey that does not decode / aggregate (deserializeSet and
-    // getAggregatedPubkey run before anything else, worker.ts:45, index.ts:160), then a
-    // signature that does not decode (maybeBatch.ts:19-24 maps fromBytes over the
-    // sets), then an infinity pubkey (verifyMultipleSignatures).  The shard reports its
-    // first error of the lowest class with its set index, so the ranks can reduce
-    // (class, call index) in that order (lodestar_amd/shard.py).
+
+  // ---- stage (partial mode, instead of the ones below): the shard's status and the
+  // product of its f.
+  // The call rejects with the code of its first error, classes in the reference's
+  // order: a pubkey that does not decode / aggregate (deserializeSet and
+  // getAggregatedPubkey run before anything else, worker.ts:45, index.ts:160), then a
+  // signature that does not decode (maybeBatch.ts:19-24 maps fromBytes over the
+  // sets), then an infinity pubkey (verifyMultipleSignatures).  The shard reports its
+  // first error of the lowest class with its set index, so the ranks can reduce
+  // (class, call index) in that order (lodestar_amd/shard.py).
+  int partial_result() {
+    const uint32_t n = sh.n, R = sh.R;
     std::vector<int32_t> st(res_host(ctx, b.req_status_host), res_host(ctx, b.req_status_host) + R);
-    *partial_status = 0;
-    for (uint32_t r = 0; r < R && !*partial_status; ++r)
-      if (st[r] != 0) *partial_status = -st[r];
-    if (*partial_status && n > 0) {
+    *a.partial_status = 0;
+    for (uint32_t r = 0; r < R && !*a.partial_status; ++r)
+      if (st[r] != 0) *a.partial_status = -st[r];
+    if (*a.partial_status && n > 0) {
       std::vector<int32_t> pks(n), sgs(n);
       std::vector<uint8_t> inf(n);
       HIPC(ctx, hipMemcpyAsync(pks.data(), b.pk_status, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));
@@ -1775,215 +1534,340 @@ static int verify_body(bls_gpu_ctx* ctx, const bls_batch* in, int32_t* verdicts,
         if (sgs[i] != BLS_OK) { cls = 1; idx = i; code = sgs[i]; }
       for (uint32_t i = 0; i < n && cls > 2; ++i)
         if (inf[i]) { cls = 2; idx = i; code = BLS_PK_IS_INFINITY; }
-      if (cls < 3) *partial_status = -code;  // else: an empty-request code (kept)
-      if (partial_err) {
-        partial_err[0] = cls;
-        partial_err[1] = idx;
+      if (cls < 3) *a.partial_status = -code;  // else: an empty-request code (kept)
+      if (a.partial_err) {
+        a.partial_err[0] = cls;
+        a.partial_err[1] = idx;
       }
     }
-    if (*partial_status || n == 0) return 0;
-    const Fp12* cur = b.f;
-    uint32_t m = n_prod, lvl = 0;
-    while (m > 1) {
-      HIPC(ctx, launch_k_fprod(cur, m, ptree[lvl & 1], nullptr, ctx->coop, s)); dbg_sync(s, "k_fprod");
-      cur = ptree[lvl & 1];
-      m = (m + FPROD_FAN - 1) / FPROD_FAN;
-      ++lvl;
-    }
-    HIPC(ctx, hipMemcpyAsync(partial_out, cur, sizeof(Fp12), hipMemcpyDeviceToHost, s));
+    if (*a.partial_status || n == 0) return 0;
+    const Fp12* prod = nullptr;
+    if (fprod_tree(ctx, b.f, sh.n_prod, ptree, nullptr, &prod, s)) return -1;
+    HIPC(ctx, hipMemcpyAsync(a.partial_out, prod, sizeof(Fp12), hipMemcpyDeviceToHost, s));
     HIPC(ctx, pass_wait(ctx, s));
-    if (stats) {
+    if (a.stats) {
       float ms = 0.f;
       HIPC(ctx, hipEventRecord(ctx->ev1, s));
       HIPC(ctx, hipEventSynchronize(ctx->ev1));
       (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
-      stats->device_ms = ms;
+      a.stats->device_ms = ms;
     }
     return 0;
   }
 
-  // Requests verified on their own: the non-batchable ones, then the failed chunks'
-  // (worker.ts:91-98).  A failed chunk of >= GT_MIN_REQS requests is group-tested
-  // instead of paying one final exponentiation per request (verify_groups below); its
-  // requests follow the directly verified ones in the list.
-  std::vector<uint32_t> indiv = plan.nonbatch_reqs;
-  std::vector<GtChunk> gt_chunks;  // [beg, end) of a group-tested chunk in indiv, its chunk
-  const uint32_t gt_min = group_test_min(ctx);
-  for (int pass = 0; pass < 2; ++pass)
-    for (uint32_t ch = 0; ch < n_chunks; ++ch) {
-      if (chunk_ok[ch] == 1) continue;
-      const uint32_t m = plan.chunk_off[ch + 1] - plan.chunk_off[ch];
-      if ((m >= gt_min) != (pass == 1)) continue;
-      const uint32_t beg = (uint32_t)indiv.size();
-      for (uint32_t k = plan.chunk_off[ch]; k < plan.chunk_off[ch + 1]; ++k) indiv.push_back(plan.chunk_reqs[k]);
-      if (pass == 1) gt_chunks.push_back({beg, (uint32_t)indiv.size(), ch});
-    }
-  const uint32_t n_direct = gt_chunks.empty() ? (uint32_t)indiv.size() : gt_chunks.front().beg;
-  // Group sums: on the aggregated path, with many requests group-tested, a group-tested
-  // request pairs no signature sum of its own; each group test pairs ONE sum over its
-  // requests' sets (run_group_tests) -- 4-6 Miller loops per failed chunk of 16 instead of
-  // 16 (group_sums_on).
-  const bool gsums = sigagg && !gt_chunks.empty() && group_sums_on(indiv.size() - n_direct);
-  const uint32_t n_sum = gsums ? n_direct : (uint32_t)indiv.size();  // requests pairing their own sum
-  std::vector<int32_t> indiv_verdict(indiv.size() + 1, 0);
-  std::vector<uint32_t> groups;  // k_fold groups; outlives the async copy (synchronised below)
-  GsumPlan indiv_gsum;           // likewise
-  if (!indiv.empty()) {
-    b.n_indiv = (uint32_t)indiv.size();
-    stage_copy(ctx, b.indiv_reqs, indiv.data(), sizeof(uint32_t) * indiv.size());  // the stream is idle
-    HIPC(ctx, hipEventRecord(ctx->ev[7], s));
-    if (sigagg) {
-      // each individually verified request pairs the sum of its own r sig:
-      // virtual sets indiv_vbase + t; a request whose sets were paired in their
-      // chunk's units or shared loops (its chunk failed) now runs their own Miller loops
-      std::vector<uint32_t> own;
-      const bool own_list = (use_units || ml_shared) && k_mln_list_ok(b);
-      // a set needs its own Miller loop again only when the first pass did not leave it
-      // one: it was paired in its chunk's unit (f_i = 1), or its f was shared with the
-      // next items of its lane (more than one item per k_mlf lane); at one item per lane
-      // or per lane pair f_i = e(r_i pk_i, H(m_i)) already
-      const bool f_shared = ml_shared && !(pass_pl == 1u || pass_pl == MLF_PAIR);
-      if (own_list) {
-        // every such set of the failed chunks' requests, in ONE launch with the requests'
-        // signature sums below (one Miller-loop latency instead of two on the failing
-        // call's path, profiles/r05_cfg5_fallback.json)
-        for (size_t t = plan.nonbatch_reqs.size(); t < indiv.size(); ++t)
-          for (uint32_t i = in->req_set_offsets[indiv[t]]; i < in->req_set_offsets[indiv[t] + 1]; ++i)
-            if (f_shared || (use_units && units.set_unit[i] != UNIT_NONE)) own.push_back(i);
-      } else if (use_units || ml_shared) {
-        // one launch per run of consecutive sets (a failed chunk's requests are adjacent)
-        uint32_t run_beg = 0, run_end = 0;
-        for (size_t t = plan.nonbatch_reqs.size(); t <= indiv.size(); ++t) {
-          const bool last = t == indiv.size();
-          const uint32_t beg = last ? 0 : in->req_set_offsets[indiv[t]], end = last ? 0 : in->req_set_offsets[indiv[t] + 1];
-          if (!last && run_end > run_beg && beg == run_end) {
-            run_end = end;
-            continue;
-          }
-          if (run_end > run_beg) {
-            alone_pl(run_end - run_beg);
-            HIPC(ctx, launch_k_mln(b, ctx->coop, run_beg, run_end - run_beg, s, true));
-            dbg_sync(s, "k_mln own");
-          }
-          run_beg = beg;
-          run_end = end;
-        }
-      }
-      std::vector<uint32_t> goff(n_sum + 1);
-      for (size_t t = 0; t <= n_sum; ++t) goff[t] = (uint32_t)t;
-      plan_gsum(in, goff, std::vector<uint32_t>(indiv.begin(), indiv.begin() + n_sum), indiv_gsum);
-      if (ensure_rs()) return -1;
-      if (indiv_gsum.seg.size() > gseg_cap) {
-        snprintf(ctx->err, sizeof(ctx->err), "group-sum plan exceeds its workspace");
-        return -3;
-      }
-      if (n_sum > 0) {  // (under group sums every request may be group-tested)
-        stage_copy(ctx, gsets_dev, indiv_gsum.gsets.data(), sizeof(uint32_t) * indiv_gsum.gsets.size());
-        stage_copy(ctx, gseg_dev, indiv_gsum.seg.data(), sizeof(uint32_t) * indiv_gsum.seg.size());
-        if (launch_gsum(ctx, b, indiv_gsum, gseg_dev, gsets_dev, gtmp, indiv_vbase, s)) return -1;
-      }
-      if (own_list) {
-        for (size_t t = 0; t < n_sum; ++t) own.push_back(indiv_vbase + (uint32_t)t);
-        if (!own.empty()) {
-          stage_copy(ctx, own_sets_dev, own.data(), sizeof(uint32_t) * own.size());
-          HIPC(ctx, launch_ml_alone(0, (uint32_t)own.size(), own_sets_dev));
-          dbg_sync(s, "k_mln own + indiv (list)");
-        }
-      } else {
-        HIPC(ctx, launch_ml_alone(indiv_vbase, n_sum, nullptr)); dbg_sync(s, "k_mln indiv");
+  // Aggregated path: each individually verified request pairs the sum of its own r sig
+  // (virtual sets indiv_vbase + t), and a request whose sets were paired in their chunk's
+  // units or shared loops (its chunk failed) now runs their own Miller loops.
+  int indiv_miller_loops() {
+    const uint32_t* req_off = in->req_set_offsets;
+    const size_t first_t = plan.nonbatch_reqs.size();
+    const bool shared = sh.use_units || sh.ml_shared;
+    const bool own_list = shared && k_mln_list_ok(b);
+    // a set needs its own Miller loop again only when the first pass did not leave it
+    // one: it was paired in its chunk's unit (f_i = 1), or its f was shared with the
+    // next items of its lane (more than one item per k_mlf lane); at one item per lane
+    // or per lane pair f_i = e(r_i pk_i, H(m_i)) already
+    const bool f_shared = sh.ml_shared && !(pass_pl == 1u || pass_pl == MLF_PAIR);
+    std::vector<uint32_t> own;
+    if (own_list) {
+      // every such set of the failed chunks' requests, in ONE launch with the requests'
+      // signature sums below (one Miller-loop latency instead of two on the failing
+      // call's path, profiles/r05_cfg5_fallback.json)
+      plan_own_sets(req_off, iv.reqs, first_t, f_shared, sh.use_units ? pl.units.set_unit.data() : nullptr, own);
+    } else if (shared) {
+      std::vector<uint32_t> runs;
+      plan_own_runs(req_off, iv.reqs, first_t, runs);
+      for (size_t k = 0; k < runs.size(); k += 2) {
+        alone_pl(runs[k + 1]);
+        HIPC(ctx, launch_k_mln(b, ctx->coop, runs[k], runs[k + 1], s, true)); dbg_sync(s, "k_mln own");
       }
     }
-    // groups of BLS_FOLD consecutive sets per request, multiplied in parallel first: as
-    // groups of BLS_FOLD1, then those partial products BLS_FOLD / BLS_FOLD1 at a time
-    bool any_fold = false;
-    for (uint32_t r : indiv) {
-      const uint32_t beg = in->req_set_offsets[r], end = in->req_set_offsets[r + 1];
-      for (uint32_t g = beg; g < end; g += BLS_FOLD1) {
-        const uint32_t ge = g + BLS_FOLD1 < end ? g + BLS_FOLD1 : end;
-        groups.push_back(g);
-        groups.push_back(ge);
-        any_fold = any_fold || ge - g > 1;
-      }
+    std::vector<uint32_t> goff(n_sum + 1);
+    for (size_t t = 0; t <= n_sum; ++t) goff[t] = (uint32_t)t;
+    plan_gsum(req_off, goff, iv.reqs, indiv_gsum);  // (the groups are the first n_sum requests)
+    if (ensure_rs()) return -1;
+    if (const int rc = check_gsum(indiv_gsum)) return rc;
+    if (n_sum > 0) {  // (under group sums every request may be group-tested)
+      stage_vec(gsets_dev, indiv_gsum.gsets);
+      stage_vec(gseg_dev, indiv_gsum.seg);
+      if (launch_gsum(indiv_gsum, gseg_dev, sh.indiv_vbase)) return -1;
     }
-    const uint32_t n_fold1 = (uint32_t)(groups.size() / 2);
-    for (uint32_t r : indiv) {
-      const uint32_t beg = in->req_set_offsets[r], end = in->req_set_offsets[r + 1];
-      for (uint32_t g = beg; g < end; g += BLS_FOLD) {
-        const uint32_t ge = g + BLS_FOLD < end ? g + BLS_FOLD : end;
-        if (ge - g <= BLS_FOLD1) continue;  // one first-level group: already folded
-        groups.push_back(g);
-        groups.push_back(ge);
+    if (own_list) {
+      for (size_t t = 0; t < n_sum; ++t) own.push_back(sh.indiv_vbase + (uint32_t)t);
+      if (!own.empty()) {
+        stage_vec(own_sets_dev, own);
+        HIPC(ctx, launch_ml_alone(0, (uint32_t)own.size(), own_sets_dev));
+        dbg_sync(s, "k_mln own + indiv (list)");
       }
+    } else {
+      HIPC(ctx, launch_ml_alone(sh.indiv_vbase, n_sum, nullptr)); dbg_sync(s, "k_mln indiv");
     }
+    return 0;
+  }
+
+  // each request's product: groups of BLS_FOLD consecutive sets multiplied in parallel
+  // first (as groups of BLS_FOLD1, then those partial products BLS_FOLD / BLS_FOLD1 at a
+  // time), then one final exponentiation per directly verified request
+  int indiv_products() {
+    plan_fold_groups(in->req_set_offsets, iv.reqs, fold);
     b.fold = 1;
     b.n_fold = 0;
-    if (any_fold) {
+    if (fold.any_fold) {
       b.fold = BLS_FOLD;
-      b.n_fold = (uint32_t)(groups.size() / 2);
-      stage_copy(ctx, b.fold_groups, groups.data(), sizeof(uint32_t) * groups.size());
-      HIPC(ctx, launch_k_fold(b, ctx->coop, b.fold_groups, n_fold1, 1, s)); dbg_sync(s, "k_fold");
-      HIPC(ctx, launch_k_fold(b, ctx->coop, b.fold_groups + 2ull * n_fold1, b.n_fold - n_fold1, BLS_FOLD1, s));
+      b.n_fold = (uint32_t)(fold.groups.size() / 2);
+      stage_vec(b.fold_groups, fold.groups);
+      HIPC(ctx, launch_k_fold(b, ctx->coop, b.fold_groups, fold.n_fold1, 1, s)); dbg_sync(s, "k_fold");
+      HIPC(ctx, launch_k_fold(b, ctx->coop, b.fold_groups + 2ull * fold.n_fold1, b.n_fold - fold.n_fold1, BLS_FOLD1, s));
       dbg_sync(s, "k_fold2");
     }
-    gbufs.n_direct = n_direct;
-    gbufs.sum_f = gsums ? b.f + indiv_vbase + n_direct : nullptr;
-    if (fe_save && b.n_indiv >= fe_min) HIPC(ctx, launch_k_indiv_simt(b, gbufs, fe_save, s));
-    else HIPC(ctx, launch_k_indiv_coop(b, ctx->coop, gbufs, s));
+    g.n_direct = iv.n_direct;
+    g.sum_f = gsums ? b.f + sh.indiv_vbase + iv.n_direct : nullptr;
+    if (fe_save && b.n_indiv >= sh.fe_min) HIPC(ctx, launch_k_indiv_simt(b, g, fe_save, s));
+    else HIPC(ctx, launch_k_indiv_coop(b, ctx->coop, g, s));
     dbg_sync(s, "k_indiv");
-    if (gt_chunks.empty()) HIPC(ctx, hipEventRecord(ctx->ev[8], s));
+    return 0;
   }
-  if (gt_chunks.empty()) HIPC(ctx, hipEventRecord(ctx->ev1, s));
-  HIPC(ctx, pass_wait(ctx, s));
-  if (!indiv.empty()) memcpy(indiv_verdict.data(), res_host(ctx, b.indiv_verdict), sizeof(int32_t) * indiv.size());
-  if (!gt_chunks.empty()) {
-    // group sums: test g's sum lands in virtual set indiv_vbase + n_direct + g (the
-    // group-tested requests' own slots, unused under group sums; a pass never has more
-    // tests than group-tested requests), paired before k_group_coop
-    GroupSums sums_fn;
+
+  // ---- stage: the requests verified on their own (bls/plan.hpp plan_indiv).  stage_ms[7]
+  // (with the group tests)
+  int individual_pass() {
+    plan_indiv(plan, chunk_ok.data(), sh.gt_min, iv);
+    // Group sums: on the aggregated path, with many requests group-tested, a group-tested
+    // request pairs no signature sum of its own; each group test pairs ONE sum over its
+    // requests' sets (group_sums) -- 4-6 Miller loops per failed chunk of 16 instead of 16
+    // (group_sums_min).
+    gsums = sh.sigagg && !iv.gt_chunks.empty() && iv.reqs.size() - iv.n_direct >= sh.gsums_min;
+    n_sum = gsums ? iv.n_direct : (uint32_t)iv.reqs.size();
+    indiv_verdict.assign(iv.reqs.size() + 1, 0);
+    if (!iv.reqs.empty()) {
+      b.n_indiv = (uint32_t)iv.reqs.size();
+      stage_vec(b.indiv_reqs, iv.reqs);  // the stream is idle
+      HIPC(ctx, hipEventRecord(ctx->ev[7], s));
+      if (sh.sigagg)
+        if (const int rc = indiv_miller_loops()) return rc;
+      if (indiv_products()) return -1;
+      if (iv.gt_chunks.empty()) HIPC(ctx, hipEventRecord(ctx->ev[8], s));
+    }
+    if (iv.gt_chunks.empty()) HIPC(ctx, hipEventRecord(ctx->ev1, s));
+    HIPC(ctx, pass_wait(ctx, s));
+    if (!iv.reqs.empty())
+      memcpy(indiv_verdict.data(), res_host(ctx, b.indiv_verdict), sizeof(int32_t) * iv.reqs.size());
+    return 0;
+  }
+
+  // Group sums (aggregated path): the tests' own signature sums, sum of r_i sig_i over
+  // their requests' sets, paired ML(-g1, .) before k_group_coop.  Test g's sum lands in
+  // virtual set indiv_vbase + n_direct + g (the group-tested requests' own slots, unused
+  // under group sums; a pass never has more tests than group-tested requests).  Returns 0,
+  // 1 when the plan does not fit the workspace (the caller tests the requests alone), < 0
+  // on an error.
+  int group_sums(const std::vector<uint32_t>& goff, const std::vector<uint32_t>& gmem) {
+    const uint32_t T = (uint32_t)(goff.size() - 1);
+    if (iv.n_direct + T > iv.reqs.size()) return 1;
+    std::vector<uint32_t> reqs(gmem.size());
+    for (size_t k = 0; k < gmem.size(); ++k) reqs[k] = iv.reqs[gmem[k]];
+    GsumPlan gp;
+    plan_gsum(in->req_set_offsets, goff, reqs, gp);
+    if (!gsum_fits(gp, sh.n, sh.R)) return 1;
+    stage_vec(gsets_dev, gp.gsets);  // the stream is idle
+    stage_vec(gseg_dev, gp.seg);
+    if (launch_gsum(gp, gseg_dev, sh.indiv_vbase + iv.n_direct)) return -1;
+    HIPC(ctx, launch_ml_alone(sh.indiv_vbase + iv.n_direct, T, nullptr)); dbg_sync(s, "k_mln group sums");
+    return 0;
+  }
+
+  // run the tests (goff: offsets into gmem, indices into the indiv list); results in gv
+  // (bit 0: passed; bit 1, with ref: its final exponentiation equals test ref[g]'s);
+  // 1 when the group sums do not fit (nothing ran)
+  int run_group_tests(const std::vector<uint32_t>& goff, const std::vector<uint32_t>& gmem, std::vector<int32_t>& gv,
+                      const std::vector<uint32_t>* ref = nullptr) {
+    gv.assign(goff.size() - 1, 0);
+    if (gv.empty()) return 0;
     if (gsums)
-      sums_fn = [&](const std::vector<uint32_t>& goff, const std::vector<uint32_t>& gmem) -> int {
-        const uint32_t T = (uint32_t)(goff.size() - 1);
-        if (n_direct + T > indiv.size()) return 1;
-        std::vector<uint32_t> reqs(gmem.size());
-        for (size_t k = 0; k < gmem.size(); ++k) reqs[k] = indiv[gmem[k]];
-        GsumPlan gp;
-        plan_gsum(in, goff, reqs, gp);
-        if (gp.gsets.size() > n || gp.seg.size() > gseg_cap || (gp.level_off.size() > 1 && gp.level_off[1] > gtmp_cap))
-          return 1;
-        stage_copy(ctx, gsets_dev, gp.gsets.data(), sizeof(uint32_t) * gp.gsets.size());  // the stream is idle
-        stage_copy(ctx, gseg_dev, gp.seg.data(), sizeof(uint32_t) * gp.seg.size());
-        if (launch_gsum(ctx, b, gp, gseg_dev, gsets_dev, gtmp, indiv_vbase + n_direct, s)) return -1;
-        HIPC(ctx, launch_ml_alone(indiv_vbase + n_direct, T, nullptr)); dbg_sync(s, "k_mln group sums");
-        return 0;
-      };
-    gbufs.ref_fe = chunk_fe_kept ? b.chunk_fe : nullptr;
-    if (const int rc = verify_groups(ctx, b, gbufs, gt_chunks, indiv_verdict, s, grp_cap, grp_mem_cap,
-                                     gsums ? &sums_fn : nullptr))
-      return rc;
+      if (const int rc = group_sums(goff, gmem)) return rc;
+    stage_vec(g.off, goff);  // the stream is idle
+    stage_vec(g.members, gmem);
+    g.n = (uint32_t)gv.size();
+    GroupBufs gg = g;
+    if (ref) stage_vec(g.ref, *ref);
+    else gg.fe = nullptr;
+    HIPC(ctx, launch_k_group_coop(b, ctx->coop, gg, s)); dbg_sync(s, "k_group_coop");
+    HIPC(ctx, pass_wait(ctx, s));
+    memcpy(gv.data(), res_host(ctx, g.verdict), sizeof(int32_t) * gv.size());
+    return 0;
+  }
+
+  int verify_groups();
+
+  // ---- stage: group tests over the failed chunks large enough for them
+  int group_tests() {
+    if (iv.gt_chunks.empty()) return 0;
+    g.ref_fe = chunk_fe_kept ? b.chunk_fe : nullptr;
+    if (const int rc = verify_groups()) return rc;
     HIPC(ctx, hipEventRecord(ctx->ev[8], s));
     HIPC(ctx, hipEventRecord(ctx->ev1, s));
     HIPC(ctx, pass_wait(ctx, s));
+    return 0;
   }
-  assemble_verdicts(in, plan, chunk_ok.data(), indiv, indiv_verdict.data(), verdicts, stats);
-  if (stats) {
+
+  // ---- stage: verdicts and stats.  stage_ms[k], k = 1 .. 6: from event k - 1 to event k
+  // ([0]: no H2D stage, ~0; [1] k_pk, [2] k_pre, [3] k_chain or k_pset, [4] the sums, [5] the
+  // Miller loops, [6] k_status + the merged check); [7]: the individual pass with its group
+  // tests (0 without one).  A flagged redo and the chunk checks fall between [6] and [7]:
+  // in device_ms only.
+  void finish() {
+    assemble_verdicts(in, plan, chunk_ok.data(), iv.reqs, indiv_verdict.data(), a.verdicts, a.stats);
+    if (!a.stats) return;
     float ms = 0.f;
     (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
-    stats->device_ms = ms;
-    // stage_ms: h2d, pk, pre, pset, exact, (unused), status+chunk, indiv
+    a.stats->device_ms = ms;
     (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev[0]);
-    stats->stage_ms[0] = ms;
+    a.stats->stage_ms[0] = ms;
     for (int i = 1; i <= 6; ++i) {
       (void)hipEventElapsedTime(&ms, ctx->ev[i - 1], ctx->ev[i]);
-      stats->stage_ms[i] = ms;
+      a.stats->stage_ms[i] = ms;
     }
-    stats->stage_ms[7] = 0.0;
-    if (!indiv.empty()) {
+    a.stats->stage_ms[7] = 0.0;
+    if (!iv.reqs.empty()) {
       (void)hipEventElapsedTime(&ms, ctx->ev[7], ctx->ev[8]);
-      stats->stage_ms[7] = ms;
+      a.stats->stage_ms[7] = ms;
     }
   }
+};
+
+// Group tests of the failed chunks iv.gt_chunks (the comment above group_test_min): pass A
+// (bls/plan.hpp plan_group_tests_a), its decode (bls/group_decode.hpp, or pass B without
+// complement inference), pass C for what is left; verdicts into indiv_verdict.
+int VerifyPass::verify_groups() {
+  std::vector<int32_t>& verdict = indiv_verdict;
+  const bool eq = sh.gt_eq_mode != 0 && g.fe;
+  GroupTestsA pa;
+  plan_group_tests_a(iv.gt_chunks, verdict.data(), eq, sh.gt_eq_mode != 2 && g.ref_fe, pa);
+  std::vector<GroupTestChunk>& cs = pa.cs;
+  if (!group_tests_fit(pa, sh.R, sh.n_chunks)) {
+    snprintf(ctx->err, sizeof(ctx->err), "group-test plan exceeds its workspace");
+    return -3;
+  }
+  std::vector<int32_t> gv;
+  std::vector<uint32_t> goff_b{0}, gmem_b, alone;  // alone: requests for pass C
+  std::vector<size_t> in_b;
+  const int rc_a = run_group_tests(pa.off, pa.members, gv, eq ? &pa.ref : nullptr);
+  if (rc_a < 0) return -1;
+  if (rc_a == 1) {  // the group sums of pass A do not fit: every request alone
+    for (const GroupTestChunk& c : cs) alone.insert(alone.end(), c.ok.begin(), c.ok.end());
+    cs.clear();
+  }
+  // complement inference: with the test of all the chunk's requests (A) beside each bit
+  // group G_j, FE(G_j) FE(rest_j) = FE(A) decides the complement too (FE(rest_j) == 1 iff
+  // FE(G_j) == FE(A)), so a single invalid request b shows as exactly one failing test per
+  // bit -- G_j where b's bit j is set, rest_j where it is clear -- and every other request
+  // sits in a passing test: no pass B.  Both G_j and rest_j failing (two or more invalid)
+  // or an index past m: pass C.
+  for (size_t i = 0; eq && i < cs.size(); ++i) {
+    const GroupTestChunk& c = cs[i];
+    const uint32_t m = (uint32_t)c.ok.size();
+    // without a whole test the whole is the failed chunk check (it failed)
+    const bool pass = c.whole && (gv[c.first] & 1) != 0;
+    const int32_t bad = group_decode(m, c.nbits, pass, gv.data() + c.first + (c.whole ? 1u : 0u));
+    if (bad < 0) {
+      alone.insert(alone.end(), c.ok.begin(), c.ok.end());
+      continue;
+    }
+    for (uint32_t k = 0; k < m; ++k) verdict[c.ok[k]] = (int32_t)k == bad ? 0 : 1;
+  }
+  if (eq) cs.clear();
+  // decode pass A; plan pass B
+  for (size_t i = 0; i < cs.size(); ++i) {
+    GroupTestChunk& c = cs[i];
+    uint32_t idx = c.first;
+    const uint32_t m = (uint32_t)c.ok.size();
+    if (c.has_err || m == 1) {
+      const bool pass = gv[idx++] == 1;
+      if (pass || m == 1) {
+        for (uint32_t t : c.ok) verdict[t] = pass ? 1 : 0;
+        continue;
+      }
+    }
+    uint32_t bad = 0;
+    for (uint32_t j = 0; j < c.nbits; ++j)
+      if (gv[idx + j] != 1) bad |= 1u << j;
+    if (bad >= m) {
+      alone.insert(alone.end(), c.ok.begin(), c.ok.end());
+      continue;
+    }
+    c.b = (int32_t)bad;
+    gmem_b.push_back(c.ok[bad]);
+    goff_b.push_back((uint32_t)gmem_b.size());
+    for (uint32_t k = 0; k < m; ++k)
+      if (k != bad) gmem_b.push_back(c.ok[k]);
+    goff_b.push_back((uint32_t)gmem_b.size());
+    in_b.push_back(i);
+  }
+  const int rc_b = in_b.empty() ? 0 : run_group_tests(goff_b, gmem_b, gv);
+  if (rc_b < 0) return -1;
+  for (size_t q = 0; q < in_b.size(); ++q) {
+    GroupTestChunk& c = cs[in_b[q]];
+    if (rc_b == 0 && gv[2 * q] == 0 && gv[2 * q + 1] == 1) {
+      for (uint32_t k = 0; k < c.ok.size(); ++k) verdict[c.ok[k]] = (int32_t)k == c.b ? 0 : 1;
+    } else {
+      alone.insert(alone.end(), c.ok.begin(), c.ok.end());
+    }
+  }
+  // pass C: one test per request
+  std::vector<uint32_t> goff_c{0};
+  for (size_t k = 0; k < alone.size(); ++k) goff_c.push_back((uint32_t)k + 1);
+  const int rc_c = run_group_tests(goff_c, alone, gv);
+  if (rc_c != 0) {
+    // one request per test always fits the request-sum workspace
+    snprintf(ctx->err, sizeof(ctx->err), "group tests: per-request sums do not fit");
+    return -3;
+  }
+  for (size_t k = 0; k < alone.size(); ++k) verdict[alone[k]] = gv[k] == 1 ? 1 : 0;
   return 0;
 }
+
+int verify_body(bls_gpu_ctx* ctx, const bls_batch* in, const PassArgs& a) {
+  HIPC(ctx, hipSetDevice(ctx->device));
+  if (a.stats) memset(a.stats, 0, sizeof(*a.stats));
+  if (in->n_reqs == 0) return 0;
+  if (const int rc = check_batch(in, "batch", ctx->err, sizeof(ctx->err))) return rc;
+  const InFlight in_flight(in->n_sets);
+  VerifyPass p(ctx, in, a);
+  int rc;
+  if ((rc = p.stage_inputs())) return rc;
+  if ((rc = p.first_pass())) return rc;
+  if ((rc = p.merged_check())) return rc;
+  if ((rc = p.flagged_redo())) return rc;
+  if ((rc = p.chunk_checks())) return rc;
+  if (p.sh.partial) return p.partial_result();
+  if ((rc = p.individual_pass())) return rc;
+  if ((rc = p.group_tests())) return rc;
+  p.finish();
+  return 0;
+}
+
+}  // namespace
+
+// One call under the context's lock.  A call that fails part-way may leave the MSM's
+// bucket counters / tickets (reset only by the kernels' last workgroups) mid-pass: they
+// are zeroed again before the context takes another call.
+static int verify_impl(bls_gpu_ctx* ctx, const bls_batch* in, int32_t* verdicts, bls_stats* stats,
+                       uint32_t scalar_base, uint8_t* partial_out, int32_t* partial_status,
+                       uint32_t* partial_err = nullptr, const std::vector<uint32_t>* req_bounds = nullptr,
+                       const SameMsgPlan* sm = nullptr) {
+  CTX_LOCK(ctx);
+  ctx->wait_block = wait_blocks(in->n_sets);
+  const int rc = verify_body(ctx, in, PassArgs{verdicts, stats, scalar_base, partial_out, partial_status, partial_err,
+                                               req_bounds, sm});
+  if (rc < 0 && ctx->msm_state) {
+    (void)hipStreamSynchronize(ctx->stream);
+    (void)hipMemsetAsync(ctx->msm_state, 0, sizeof(uint32_t) * MSM_STATE_WORDS, ctx->stream);
+    (void)hipStreamSynchronize(ctx->stream);
+  }
+  return rc;
+}
+
+extern "C" {
 
 int bls_gpu_verify(bls_gpu_ctx* ctx, const bls_batch* in, int32_t* verdicts, bls_stats* stats) {
   return verify_impl(ctx, in, verdicts, stats, 0u, nullptr, nullptr);
@@ -2028,7 +1912,7 @@ int bls_gpu_verify_many(bls_gpu_ctx* ctx, const bls_batch* batches, uint32_t n_b
     const bls_batch& b = batches[k];
     char what[32];
     snprintf(what, sizeof(what), "batch %u", k);
-    if (const int rc = check_batch(ctx, &b, what)) return rc;
+    if (const int rc = check_batch(&b, what, ctx->err, sizeof(ctx->err))) return rc;
     if (b.n_reqs == 0 && b.n_sets != 0) {
       snprintf(ctx->err, sizeof(ctx->err), "%s: sets without requests", what);
       return -2;
@@ -2145,15 +2029,7 @@ int bls_gpu_final_check(bls_gpu_ctx* ctx, const uint8_t* partials, uint32_t n, i
   int32_t* dv = d.take<int32_t>(1);
   hipStream_t s = ctx->stream;
   HIPC(ctx, hipMemcpyAsync(in, partials, 576ull * n, hipMemcpyHostToDevice, s));
-  const Fp12* cur = in;
-  uint32_t m = n, lvl = 0;
-  while (m > FPROD_FAN) {
-    HIPC(ctx, launch_k_fprod(cur, m, t[lvl & 1], nullptr, ctx->coop, s));
-    cur = t[lvl & 1];
-    m = (m + FPROD_FAN - 1) / FPROD_FAN;
-    ++lvl;
-  }
-  HIPC(ctx, launch_k_fprod(cur, m, nullptr, dv, ctx->coop, s));
+  if (fprod_tree(ctx, in, n, t, dv, nullptr, s)) return -1;
   HIPC(ctx, hipMemcpyAsync(verdict, dv, sizeof(int32_t), hipMemcpyDeviceToHost, s));
   HIPC(ctx, hipStreamSynchronize(s));
   return 0;

@@ -60,7 +60,6 @@ hipError_t launch_k_uset(const bls::PipeBufs& b, const bls::G1J* sums, const uin
 // same-message jobs (kernels/k_smsg.hip): chunk c's sum r_i pk_i -> unit b.unit_base + c and
 // sum r_i sig_i -> virtual set b.n_sets + c, one wavefront per chunk (one unit per chunk)
 hipError_t launch_k_smsum(const bls::PipeBufs& b, const uint32_t* unit_rep, hipStream_t s);
-#define GSUM_FAN 4u  // points per k_gsum segment (a 16-set chunk: two levels of 3 additions)
 hipError_t launch_k_hash_to_g2(const uint8_t* msgs, uint32_t n, uint8_t* out192, hipStream_t s);
 hipError_t launch_k_sig_aggregate(const uint8_t* in96, uint32_t n, const uint32_t* off, uint32_t n_lists,
                                   bls::G2A* pts, int32_t* sig_codes, uint8_t* out96, int32_t* codes, hipStream_t s);
@@ -94,8 +93,6 @@ hipError_t launch_k_fold(const bls::PipeBufs& b, const bls::CoopEnv& env, const 
 uint32_t fe_simt_min();
 hipError_t launch_k_chunk_simt(const bls::PipeBufs& b, bls::Fp12* save, hipStream_t s);
 hipError_t launch_k_indiv_simt(const bls::PipeBufs& b, const bls::GroupBufs& g, bls::Fp12* save, hipStream_t s);
-#define BLS_FOLD 16u  // sets per k_fold group (what k_indiv strides by)
-#define BLS_FOLD1 4u  // sets per first-level k_fold group
 hipError_t launch_k_coop_probe(const bls::CoopEnv& env, bls::CoopProg pg, uint32_t blocks, uint32_t reps,
                                uint32_t* sink, uint64_t* stamps, hipStream_t s);
 // test: run program pg once on n_frames caller frames of `frame` slots (the program's own

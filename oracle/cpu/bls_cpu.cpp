@@ -34,6 +34,7 @@
 #include "bls/hash_to_curve.hpp"
 #include "bls/pairing.hpp"
 #include "bls/pipeline.hpp"
+#include "bls/plan.hpp"
 
 unsigned long long bls_fpm_counter = 0;
 

@@ -15,6 +15,7 @@
 #include "bls/pairing.hpp"
 #include "bls/hash_to_curve.hpp"
 #include "bls/pipeline.hpp"
+#include "bls/plan.hpp"
 #include "bls/group_decode.hpp"
 #include "bls/selftest_ops.hpp"
 
@@ -512,3 +513,5 @@ void hs_lz_fp2_ops(const uint8_t* a, const uint8_t* b, uint8_t* out) {
 
 }  // extern "C"
 
+// ---- bls/plan.hpp: the host-side planners of a verify pass (hs_plan_*, hs_check_batch)
+#include "plan_exports.hpp"

@@ -1,7 +1,7 @@
 // TEST INFRASTRUCTURE ONLY -- never linked into the product library.
 //
 // CPU restatement of kernels/k_smsg.hip's k_smsum and of the host-side plan of a
-// same-message call: the identical bodies (bls/smsum.hpp, bls/pipeline.hpp
+// same-message call: the identical bodies (bls/smsum.hpp, bls/plan.hpp
 // plan_same_message / check_same_message) compiled for the host, the kernel's wavefront
 // replaced by a loop over the 64 lanes of every step.  For job sizes at the lane-stride
 // and wavefront-tail edges, with some sets not live, the tree's two sums must equal a
@@ -16,6 +16,7 @@
 #include <vector>
 
 #define BLS_LAZY_POW 1
+#include "bls/plan.hpp"
 #include "bls/smsum.hpp"
 
 unsigned long long bls_fpm_counter = 0;

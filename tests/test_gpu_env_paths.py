@@ -6,7 +6,7 @@ tokens, multithread/worker.ts:32-108), the pass shape against the rule that pick
 
 * msm_flip (BLS_MSM=1): the Pippenger signature sum runs on a context whose last pass
   passed its merged check, and not on the pass after a failing one, which checks its
-  chunks straight away (bls_gpu.hip verify_body merged_skipped, ctx->last_merged_failed):
+  chunks straight away (bls_gpu.hip plan_pass: PassShape::merged_skipped, ctx->last_merged_failed):
   a failing call, then two passing ones -- pass_shape bit 0 goes 1, 0, 1, merged_check
   2, 3, 1, and every verdict is right.
 * fallbacks (BLS_COOP_ML_MAX=1, BLS_INDIV2_MAX=0, BLS_PACK3_INFLIGHT=0): a failing

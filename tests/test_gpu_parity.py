@@ -895,7 +895,7 @@ def test_failed_chunk_requests_verified_alone(gpu, oracle, table, n, bad):
 
 
 def test_failed_chunks_group_tested(gpu, oracle, table, verify_path):
-    """Failed chunks are group-tested (bls_gpu.hip verify_groups: the test of all the
+    """Failed chunks are group-tested (bls_gpu.hip VerifyPass::verify_groups: the test of all the
     chunk's requests beside its bit-index groups, each group's final exponentiation also
     compared with the whole's, so a single invalid request is decoded in one round, else
     every request alone): one

@@ -247,7 +247,7 @@ def test_fp12_pair_halves(hostsim):
 
 
 def test_group_decode_complement_inference(hostsim):
-    """bls_gpu.hip verify_groups' decode of a failed chunk (bls/group_decode.hpp) against a
+    """bls_gpu.hip VerifyPass::verify_groups' decode of a failed chunk (bls/group_decode.hpp) against a
     model of the tests: each request's final exponentiation is a group element (1 for a
     valid request; a random non-identity one for an invalid), a test's value the product
     over its requests.  With one invalid request the decode names it (the others valid);

@@ -1,6 +1,6 @@
 """bls_gpu_verify_same_message without a GPU: the binding and its argument checks, and the
 CPU restatement of k_smsum's reduction tree and of the call's host-side plan
-(tests/native/smsum_host.cpp: the same bls/smsum.hpp and bls/pipeline.hpp bodies compiled
+(tests/native/smsum_host.cpp: the same bls/smsum.hpp and bls/plan.hpp bodies compiled
 for the host), once plain and once under AddressSanitizer + UBSan as a stand-alone
 program."""
 from __future__ import annotations
