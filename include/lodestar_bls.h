@@ -232,6 +232,56 @@ typedef struct bls_same_msg_batch {
 int bls_gpu_verify_same_message(bls_gpu_ctx* ctx, const bls_same_msg_batch* batch, int32_t* set_verdicts,
                                 bls_stats* stats);
 
+/* Deposit signatures (state-transition/src/block/processDeposit.ts:48-65): the one
+ * signature check of the beacon node outside IBlsVerifier.  For a deposit of an unknown
+ * validator the reference runs, inside one try block whose catch skips the deposit,
+ *     PublicKey.fromBytes(pubkey, CoordType.affine, true)      -- KeyValidate, untrusted key
+ *     Signature.fromBytes(signature, CoordType.affine, true)
+ *     verify(publicKey, computeSigningRoot(DepositMessage, deposit, domain), signature)
+ * with domain = computeDomain(DOMAIN_DEPOSIT, fork_version, ZERO_HASH) (:52).  One call
+ * checks n deposits given by their four fields. */
+#define BLS_DEPOSITS_MAX_CALL 65536u
+typedef struct bls_deposit_batch {
+  uint32_t n;
+  const uint8_t* pubkeys48;               /* n * 48 compressed G1, untrusted */
+  const uint8_t* withdrawal_credentials;  /* n * 32 */
+  const uint8_t* amounts;                 /* n * 8, little-endian Gwei as in the SSZ serialization */
+  const uint8_t* signatures;              /* n * 96 compressed G2 */
+  const uint8_t* domain;                  /* 32 bytes: compute_domain(DOMAIN_DEPOSIT, fork_version, zero root) */
+  const uint8_t* seed;                    /* as in bls_batch */
+} bls_deposit_batch;
+
+/* verdicts: n int32.  verdicts[i] is what the reference's try block gives deposit i on its
+ * own: 1 valid, 0 invalid, -code when a step throws.  The order of the steps fixes the code:
+ *   1. KeyValidate of the key: BLS_CODE_BAD_ENCODING, POINT_NOT_ON_CURVE, PK_IS_INFINITY or
+ *      POINT_NOT_IN_GROUP;
+ *   2. the signature decoded with validation: BAD_ENCODING, POINT_NOT_ON_CURVE,
+ *      POINT_NOT_IN_GROUP;
+ *   3. the one-set rules of bls_gpu_verify: an infinity signature BLS_CODE_ZERO_SIGNATURE;
+ *   4. verify(pk, signing_root), the root being hash_tree_root(SigningData{
+ *      hash_tree_root(DepositMessage{pubkey, withdrawal_credentials, amount}), domain}),
+ *      computed on the device (signingRoot.ts:7-13).
+ * An invalid deposit is legal: it never makes the call fail, and no verdict depends on
+ * another deposit of the call.  The device table is neither read nor written.
+ *
+ * Internally every deposit is one batchable one-set request of the bls_gpu_verify pass:
+ * chunks of chunkifyMaximizeChunkSize(n, 16), the merged check, the per-request fallback
+ * and the group tests, so the verdicts are those of per-deposit verification apart from
+ * the 2^-64 of a random-scalar batch.  Soundness of batching untrusted keys: a random-
+ * scalar batch is sound only over points of the prime-order groups, so a deposit whose
+ * key or signature has an error code gives its request that status before any product is
+ * formed -- the key stage hands on the point at infinity for it -- and a key outside G1
+ * never enters a batch.
+ *
+ * stats (nullable): those of bls_gpu_verify over n one-set batchable requests;
+ * n_unique_msgs == n (the roots are made on the device, so there is no signing-root
+ * dedup).  Like a same-message call, a deposit call neither reads nor writes the
+ * context's merged-check history: invalid deposits are normal and must not change the
+ * shape of the next gossip pass.
+ * n == 0 returns 0 and writes nothing; n > BLS_DEPOSITS_MAX_CALL, or a NULL pointer other
+ * than seed or stats, returns -2. */
+int bls_gpu_verify_deposits(bls_gpu_ctx* ctx, const bls_deposit_batch* batch, int32_t* verdicts, bls_stats* stats);
+
 /* Sharded call across GPUs (north_star "each GPU reduces its shard to
  * an Fp12 partial, the partials are combined over RCCL/xGMI, and one final
  * exponentiation follows").  The reference verifies one call as ONE random-scalar

@@ -45,6 +45,15 @@
  * 1 (an error code is false).  Sets whose publicKey is not a table index (raw 96-byte
  * keys) do not enter the batch: each goes through the existing path as a one-set
  * batchable request.
+ *
+ * verifyDeposits(deposits, {forkVersion | domain}) -> Promise<boolean[]> (processDeposit.ts:
+ * 48-65, the one signature check outside IBlsVerifier): deposits are {pubkey: Uint8Array(48),
+ * withdrawalCredentials: Uint8Array(32), amount: bigint | number (Gwei), signature}.  Each call,
+ * or each part of at most DEPOSITS_MAX_CALL deposits, is a job of its own kind that an idle
+ * context of the least-loaded slot runs as ONE addon.verifyDeposits call
+ * (bls_gpu_verify_deposits): KeyValidate of the untrusted keys, the signing roots and the
+ * verification all on the GPU, the device tables untouched.  An invalid deposit resolves
+ * false and never rejects; the promise rejects only for a runtime failure.
  * Plain CommonJS so it runs on the Node in this image (v12); the TypeScript
  * version is the same code with the reference's types.
  */
@@ -79,6 +88,8 @@ const GPU_SETS_PER_CALL = 1024; // sets per bls_gpu_verify call (cfg2 shape)
 const MAX_BUFFERED_SIGS = 32; // multithread/index.ts:48
 const MAX_BUFFER_WAIT_MS = 100; // multithread/index.ts:57
 const SPLIT_CALL_MIN_SETS = 4096; // non-batchable calls this large are split across device slots
+const DEPOSITS_MAX_CALL = 65536; // BLS_DEPOSITS_MAX_CALL
+const DOMAIN_DEPOSIT = Buffer.from("03000000", "hex");
 const AGG_KEY_WEIGHT = 1024; // keys of an aggregate set per set of routing weight (setWeight)
 
 const ERROR_MESSAGES = {
@@ -187,6 +198,43 @@ function packSameMessage(jobs, seed) {
     jobSetOffsets[j + 1] = k;
   }
   return {jobSetOffsets, messages, pkIndices, signatures, seed: seed || null};
+}
+
+/** compute_domain(DOMAIN_DEPOSIT, forkVersion, genesisValidatorsRoot = zero root)
+ * (util/domain.ts:27-45): the domain type, then the first 28 bytes of
+ * hash_tree_root(ForkData{forkVersion, root}) -- one SHA-256 over two chunks. */
+function depositDomain(forkVersion, genesisValidatorsRoot) {
+  if (forkVersion.length !== 4) throw Error("forkVersion is 4 bytes");
+  const root = genesisValidatorsRoot || Buffer.alloc(32);
+  if (root.length !== 32) throw Error("genesisValidatorsRoot is 32 bytes");
+  const chunk = Buffer.alloc(32);
+  chunk.set(forkVersion, 0);
+  const forkDataRoot = require("crypto").createHash("sha256").update(chunk).update(root).digest();
+  return Buffer.concat([DOMAIN_DEPOSIT, forkDataRoot.subarray(0, 28)]);
+}
+
+/** Pack deposits ({pubkey, withdrawalCredentials, amount, signature}) into the SoA request
+ * of addon.verifyDeposits (bls_deposit_batch); every signature must be 96 bytes. */
+function packDeposits(deposits, domain, seed) {
+  const n = deposits.length;
+  if (domain.length !== 32) throw Error("the deposit domain is 32 bytes");
+  const pubkeys = Buffer.alloc(48 * n);
+  const withdrawalCredentials = Buffer.alloc(32 * n);
+  const amounts = Buffer.alloc(8 * n);
+  const signatures = Buffer.alloc(96 * n);
+  for (let k = 0; k < n; k++) {
+    const d = deposits[k];
+    if (d.pubkey.length !== 48) throw Error("deposit pubkeys are 48 bytes (compressed G1)");
+    if (d.withdrawalCredentials.length !== 32) throw Error("withdrawal credentials are 32 bytes");
+    if (d.signature.length !== 96) throw Error("deposit signatures are 96 bytes (compressed G2)");
+    const amount = BigInt(d.amount);
+    if (amount < 0n || amount >= 1n << 64n) throw Error("a deposit amount is a uint64 (Gwei)");
+    pubkeys.set(d.pubkey, 48 * k);
+    withdrawalCredentials.set(d.withdrawalCredentials, 32 * k);
+    amounts.writeBigUInt64LE(amount, 8 * k);
+    signatures.set(d.signature, 96 * k);
+  }
+  return {pubkeys, withdrawalCredentials, amounts, signatures, domain: Buffer.from(domain), seed: seed || null};
 }
 
 /** Contiguous [beg, end) shards of n sets over `parts` devices, sizes differing by at
@@ -302,6 +350,7 @@ class GpuBlsVerifier {
     this.jobs = []; // queue: jobs[jobsHead..] are pending
     this.jobsHead = 0;
     this.smJobs = []; // same-message jobs ({message, indices, signatures, resolve, reject}), their own kind
+    this.depJobs = []; // deposit jobs ({deposits, domain, resolve, reject}): one addon.verifyDeposits call each
     this.runScheduled = false;
     this.bufJobs = []; // batchable jobs waiting for > 32 sigs or 100 ms (index.ts:262-279)
     this.bufSigs = 0;
@@ -414,6 +463,44 @@ class GpuBlsVerifier {
     return Promise.all(parts).then(() => out);
   }
 
+  /**
+   * processDeposit's signature check (processDeposit.ts:48-65) for a list of deposits:
+   * Promise<boolean[]>, true iff the deposit's key validates, its signature decodes and
+   * verifies over its DepositMessage signing root.  opts: {forkVersion} (the domain is
+   * computed here) or {domain}.  Never rejects for an invalid deposit (a signature of the
+   * wrong length is false without a GPU call); rejects only for a runtime failure.
+   */
+  verifyDeposits(deposits, opts) {
+    const o = opts || NO_OPTS;
+    let domain;
+    try {
+      if ((o.domain === undefined) === (o.forkVersion === undefined)) throw Error("give forkVersion or domain");
+      domain = o.domain !== undefined ? o.domain : depositDomain(o.forkVersion);
+      if (domain.length !== 32) throw Error("the deposit domain is 32 bytes");
+    } catch (e) {
+      return Promise.reject(e);
+    }
+    const n = deposits.length;
+    if (n === 0) return Promise.resolve([]);
+    if (this.closed) return Promise.reject(Error("QUEUE_ABORTED"));
+    if (this.ctxs.length === 0 && this.initErrors.length > 0) return Promise.reject(this.initErrors[0]);
+    const out = new Array(n).fill(false);
+    const taken = [];
+    for (let k = 0; k < n; k++) if (deposits[k].signature.length === 96) taken.push(k);
+    const parts = [];
+    for (let first = 0; first < taken.length; first += DEPOSITS_MAX_CALL) {
+      const pos = taken.slice(first, first + DEPOSITS_MAX_CALL);
+      parts.push(new Promise((resolve, reject) => {
+        this.depJobs.push({deposits: pos.map((k) => deposits[k]), domain, resolve, reject,
+                           addedTimeMs: this.metrics ? Date.now() : 0});
+        this._scheduleRun();
+      }).then((codes) => {
+        for (let i = 0; i < pos.length; i++) out[pos[i]] = codes[i] === 1;
+      }));
+    }
+    return Promise.all(parts).then(() => out);
+  }
+
   /** The reference's path for a call: chunkifyMaximizeChunkSize(sets, 128) jobs, AND-ed. */
   _queueCall(sets, batchable) {
     return Promise.all(
@@ -520,8 +607,9 @@ class GpuBlsVerifier {
     this.closed = true;
     if (this.bufTimer) clearTimeout(this.bufTimer);
     this.bufTimer = null;
-    const pending = this.jobs.slice(this.jobsHead).concat(this.bufJobs, this.smJobs);
+    const pending = this.jobs.slice(this.jobsHead).concat(this.bufJobs, this.smJobs, this.depJobs);
     this.smJobs = [];
+    this.depJobs = [];
     const pinned = [].concat(...this.pinned);
     this.jobs = [];
     this.jobsHead = 0;
@@ -632,7 +720,7 @@ class GpuBlsVerifier {
           this._startPinned(ctx, this.pinned[s].shift());
         }
       }
-      if (this.jobsHead >= this.jobs.length && this.smJobs.length === 0) return;
+      if (this.jobsHead >= this.jobs.length && this.smJobs.length === 0 && this.depJobs.length === 0) return;
       let ctx = null;
       let best = Infinity;
       for (let s = 0; s < this.nSlots; s++) {
@@ -645,6 +733,7 @@ class GpuBlsVerifier {
       }
       if (ctx === null) return;
       if (this.smJobs.length > 0) this._startSameMessageJobs(ctx);
+      else if (this.depJobs.length > 0) this._startDepositJob(ctx);
       else this._startJobs(ctx);
     }
   }
@@ -738,6 +827,53 @@ class GpuBlsVerifier {
         j.resolve(verdicts.subarray(k, k + j.indices.length));
         k += j.indices.length;
       }
+      this._dispatch();
+    }, fail);
+  }
+
+  /** One deposit job in one addon.verifyDeposits call; it resolves to its deposits' codes. */
+  _startDepositJob(ctx) {
+    const j = this.depJobs.shift();
+    const total = j.deposits.length;
+    const weight = total; // a deposit weighs one single-key set
+    const tp = this.metrics && this.metrics.blsThreadPool;
+    this.stats.jobGroupsStarted += 1;
+    this.stats.jobsStarted += 1;
+    this.stats.sigSetsStarted += total;
+    const st = this.slotStats[ctx.slot];
+    st.calls++;
+    st.sets += total;
+    st.weight += weight;
+    if (tp) {
+      tp.jobWaitTime.observe((Date.now() - j.addedTimeMs) / 1000);
+      tp.totalJobsGroupsStarted.inc(1);
+      tp.totalJobsStarted.inc(1);
+      tp.totalSigSetsStarted.inc(total);
+    }
+    this.slotLoad[ctx.slot] += weight;
+    const fail = (e) => {
+      this.slotLoad[ctx.slot] -= weight;
+      j.reject(e);
+      if (tp) tp.errorJobsSignatureSetsCount.inc(total);
+      this._dispatch();
+    };
+    let req;
+    try {
+      req = packDeposits(j.deposits, j.domain);
+    } catch (e) {
+      fail(e);
+      return;
+    }
+    this._run(ctx, () => this.addon.verifyDeposits(ctx.handle, req)).then((verdicts) => {
+      this.slotLoad[ctx.slot] -= weight;
+      this.stats.batchRetries += verdicts.batchRetries || 0;
+      this.stats.batchSigsSuccess += verdicts.batchSigsSuccess || 0;
+      if (tp) {
+        tp.batchRetries.inc(verdicts.batchRetries || 0);
+        tp.batchSigsSuccess.inc(verdicts.batchSigsSuccess || 0);
+        tp.successJobsSignatureSetsCount.inc(total);
+      }
+      j.resolve(verdicts);
       this._dispatch();
     }, fail);
   }
@@ -851,6 +987,9 @@ module.exports = {
   chunkifyMaximizeChunkSize,
   packRequests,
   packSameMessage,
+  packDeposits,
+  depositDomain,
+  DEPOSITS_MAX_CALL,
   shardBounds,
   setWeight,
   getAggregatedPubkeysCount,

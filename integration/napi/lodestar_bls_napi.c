@@ -18,6 +18,11 @@
  *          -> Promise<Int32Array set verdicts>   (bls_gpu_verify_same_message: jobs of table-index
  *          sets that sign one root each, IBlsVerifier.verifySignatureSetsSameMessage; the array
  *          also carries nChunks = jobs batched and nIndividual = sets verified on their own)
+ *   verifyDeposits(handle, {pubkeys, withdrawalCredentials, amounts, signatures, domain, seed?})
+ *          -> Promise<Int32Array verdicts>   (bls_gpu_verify_deposits: n = pubkeys.length / 48
+ *          deposits by their four fields, amounts 8 B little-endian each; one code per deposit,
+ *          1 valid, 0 invalid, -code a step that throws in processDeposit.ts:48-65; an invalid
+ *          deposit never rejects the promise)
  *   close(handle)
  *
  * The verdict array carries the worker's BlsWorkResult bookkeeping (types.ts:26-38) as
@@ -198,7 +203,7 @@ static napi_value js_load_pubkeys(napi_env env, napi_callback_info info) {
   return out;
 }
 
-enum { JOB_VERIFY = 0, JOB_PARTIAL = 1, JOB_FINAL = 2, JOB_SAME_MSG = 3 };
+enum { JOB_VERIFY = 0, JOB_PARTIAL = 1, JOB_FINAL = 2, JOB_SAME_MSG = 3, JOB_DEPOSITS = 4 };
 
 typedef struct {
   int kind;
@@ -206,6 +211,7 @@ typedef struct {
   bls_gpu_ctx* ctx;
   bls_batch batch;
   bls_same_msg_batch same;  /* JOB_SAME_MSG */
+  bls_deposit_batch dep;    /* JOB_DEPOSITS */
   napi_ref keep;          /* the request object: keeps the input buffers alive */
   napi_ref keep_handle;   /* the handle object: no finalizer while the job is out */
   int32_t* verdicts;
@@ -255,6 +261,8 @@ static void verify_execute(napi_env env, void* data) {
     j->rc = bls_gpu_final_check(j->ctx, j->partials, j->n_partials, &j->verdict);
   else if (j->kind == JOB_SAME_MSG)
     j->rc = bls_gpu_verify_same_message(j->ctx, &j->same, j->verdicts, &j->stats);
+  else if (j->kind == JOB_DEPOSITS)
+    j->rc = bls_gpu_verify_deposits(j->ctx, &j->dep, j->verdicts, &j->stats);
   else
     j->rc = bls_gpu_verify(j->ctx, &j->batch, j->verdicts, &j->stats);
   j->t_end_ns = mono_ns();
@@ -268,7 +276,8 @@ static void verify_complete(napi_env env, napi_status status, void* data) {
     snprintf(text, sizeof(text), "%s failed (rc %d, status %d): %s",
              j->kind == JOB_PARTIAL ? "bls_gpu_partial"
              : j->kind == JOB_FINAL ? "bls_gpu_final_check"
-             : j->kind == JOB_SAME_MSG ? "bls_gpu_verify_same_message" : "bls_gpu_verify",
+             : j->kind == JOB_SAME_MSG ? "bls_gpu_verify_same_message"
+             : j->kind == JOB_DEPOSITS ? "bls_gpu_verify_deposits" : "bls_gpu_verify",
              j->rc, (int)status,
              j->rc ? bls_gpu_last_error(j->ctx) : "cancelled");
     napi_create_string_utf8(env, text, NAPI_AUTO_LENGTH, &msg);
@@ -305,12 +314,12 @@ static void verify_complete(napi_env env, napi_status status, void* data) {
   } else {
     napi_value ab, out;
     void* dst;
-    uint32_t n = j->kind == JOB_SAME_MSG ? j->same.n_sets : j->batch.n_reqs;
+    uint32_t n = j->kind == JOB_SAME_MSG ? j->same.n_sets : j->kind == JOB_DEPOSITS ? j->dep.n : j->batch.n_reqs;
     napi_create_arraybuffer(env, 4 * (size_t)(n ? n : 1), &dst, &ab);
     memcpy(dst, j->verdicts, 4 * (size_t)n);
     napi_create_typedarray(env, napi_int32_array, n, ab, 0, &out);
     attach_stats(env, out, &j->stats, j->t_start_ns, j->t_end_ns);
-    if (j->kind == JOB_SAME_MSG) {
+    if (j->kind == JOB_SAME_MSG || j->kind == JOB_DEPOSITS) {
       napi_value v;
       napi_create_uint32(env, j->stats.n_chunks, &v);
       napi_set_named_property(env, out, "nChunks", v);
@@ -444,6 +453,47 @@ static napi_value js_verify_same_message(napi_env env, napi_callback_info info) 
   j->same.signatures = (const uint8_t*)sig;
   j->same.seed = nseed >= 32 ? (const uint8_t*)seed : NULL;
   j->verdicts = (int32_t*)calloc(n_sets ? n_sets : 1, 4);
+  return queue_job(env, h, j, argv[0], argv[1]);
+}
+
+/* verifyDeposits(handle, {pubkeys, withdrawalCredentials, amounts, signatures, domain, seed?})
+ * -> Promise<Int32Array>: bls_gpu_verify_deposits on a libuv worker, one code per deposit.
+ * n = pubkeys.length / 48; every other buffer must hold what n says. */
+static napi_value js_verify_deposits(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  bls_handle* h = argc >= 2 ? get_handle(env, argv[0]) : NULL;
+  if (!h) {
+    napi_throw_type_error(env, NULL, "verifyDeposits(handle, request): no live handle (closed?)");
+    return NULL;
+  }
+  void *pks, *wc, *amt, *sig, *dom, *seed;
+  size_t npks, nwc, namt, nsig, ndom, nseed;
+  if (prop(env, argv[1], "pubkeys", &pks, &npks) || prop(env, argv[1], "withdrawalCredentials", &wc, &nwc) ||
+      prop(env, argv[1], "amounts", &amt, &namt) || prop(env, argv[1], "signatures", &sig, &nsig) ||
+      prop(env, argv[1], "domain", &dom, &ndom) || prop(env, argv[1], "seed", &seed, &nseed) || npks % 48 != 0) {
+    napi_throw_type_error(env, NULL, "verifyDeposits: bad request object");
+    return NULL;
+  }
+  const size_t n = npks / 48;
+  if (n > BLS_DEPOSITS_MAX_CALL || nwc < 32 * n || namt < 8 * n || nsig < 96 * n || ndom < 32 ||
+      (n > 0 && (!pks || !wc || !amt || !sig || !dom))) {
+    napi_throw_range_error(env, NULL, "verifyDeposits: more than BLS_DEPOSITS_MAX_CALL deposits, or a buffer is "
+                                      "shorter than n requires (pubkeys 48 B, withdrawalCredentials 32 B, amounts "
+                                      "8 B, signatures 96 B per deposit; domain 32 B)");
+    return NULL;
+  }
+  verify_job* j = (verify_job*)calloc(1, sizeof(verify_job));
+  j->kind = JOB_DEPOSITS;
+  j->dep.n = (uint32_t)n;
+  j->dep.pubkeys48 = (const uint8_t*)pks;
+  j->dep.withdrawal_credentials = (const uint8_t*)wc;
+  j->dep.amounts = (const uint8_t*)amt;
+  j->dep.signatures = (const uint8_t*)sig;
+  j->dep.domain = (const uint8_t*)dom;
+  j->dep.seed = nseed >= 32 ? (const uint8_t*)seed : NULL;
+  j->verdicts = (int32_t*)calloc(n ? n : 1, 4);
   return queue_job(env, h, j, argv[0], argv[1]);
 }
 
@@ -595,6 +645,7 @@ static napi_value module_init(napi_env env, napi_value exports) {
       {"partial", NULL, js_partial, NULL, NULL, NULL, napi_default, NULL},
       {"finalCheck", NULL, js_final_check, NULL, NULL, NULL, napi_default, NULL},
       {"verifySameMessage", NULL, js_verify_same_message, NULL, NULL, NULL, napi_default, NULL},
+      {"verifyDeposits", NULL, js_verify_deposits, NULL, NULL, NULL, napi_default, NULL},
   };
   napi_define_properties(env, exports, sizeof(d) / sizeof(d[0]), d);
   return exports;

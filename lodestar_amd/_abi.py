@@ -49,6 +49,7 @@ SYMBOLS = (
     "bls_gpu_verify",
     "bls_gpu_verify_many",
     "bls_gpu_verify_same_message",
+    "bls_gpu_verify_deposits",
     "bls_gpu_aggregate_pubkeys",
     "bls_gpu_validate_pubkeys",
     "bls_gpu_partial",
@@ -141,6 +142,23 @@ class BlsSameMsgBatch(ctypes.Structure):
 SAME_MSG_MAX_JOB = 4096  # BLS_SAME_MSG_MAX_JOB
 
 
+class BlsDepositBatch(ctypes.Structure):
+    """bls_deposit_batch: n deposits by their four fields, one domain for the call"""
+
+    _fields_ = [
+        ("n", ctypes.c_uint32),
+        ("pubkeys48", ctypes.c_void_p),
+        ("withdrawal_credentials", ctypes.c_void_p),
+        ("amounts", ctypes.c_void_p),
+        ("signatures", ctypes.c_void_p),
+        ("domain", ctypes.c_void_p),
+        ("seed", ctypes.c_void_p),
+    ]
+
+
+DEPOSITS_MAX_CALL = 65536  # BLS_DEPOSITS_MAX_CALL
+
+
 class BlsAdmission(ctypes.Structure):
     _fields_ = [
         ("contexts_normal", ctypes.c_uint32),
@@ -191,6 +209,8 @@ def bind(lib: ctypes.CDLL) -> ctypes.CDLL:
         lib.bls_gpu_verify_many.restype = i32
         lib.bls_gpu_verify_same_message.argtypes = [vp, ctypes.POINTER(BlsSameMsgBatch), vp, ctypes.POINTER(BlsStats)]
         lib.bls_gpu_verify_same_message.restype = i32
+        lib.bls_gpu_verify_deposits.argtypes = [vp, ctypes.POINTER(BlsDepositBatch), vp, ctypes.POINTER(BlsStats)]
+        lib.bls_gpu_verify_deposits.restype = i32
         lib.bls_gpu_validate_pubkeys.argtypes = [vp, vp, u32, u32, vp]
         lib.bls_gpu_validate_pubkeys.restype = i32
         lib.bls_gpu_partial.argtypes = [vp, ctypes.POINTER(BlsBatch), u32, vp, vp, vp, ctypes.POINTER(BlsStats)]

@@ -299,6 +299,12 @@ def build_plan_host(verbose: bool = True, out: Path | None = None, extra: list[s
     return _build_host_program("plan_host", ("plan_exports.hpp",), verbose, out, extra)
 
 
+def build_deposit_host(verbose: bool = True, out: Path | None = None, extra: list[str] | None = None) -> Path:
+    """The deposit front kernel's per-item stages (bls/deposit.hpp) on records from a file or
+    stdin (tests/native/deposit_host.cpp), a stand-alone program for tests/; `extra` as above."""
+    return _build_host_program("deposit_host", (), verbose, out, extra)
+
+
 def build_cpu_baseline(verbose: bool = True) -> Path:
     """The C++ CPU baseline under oracle/cpu (benchmark / test infrastructure, "not
     blst"; oracle/cpu/bls_cpu.cpp), next to its source: bench.py's cpu_baseline leg
@@ -341,4 +347,5 @@ if __name__ == "__main__":
     build_hostsim()
     build_smsum_host()
     build_plan_host()
+    build_deposit_host()
     build_cpu_baseline()

@@ -162,6 +162,39 @@ inline void plan_same_message(const bls_same_msg_batch* in, SameMsgPlan& p) {
   }
 }
 
+// Plan of one bls_gpu_verify_deposits call over the verify pass: every deposit is a one-set
+// batchable request (request index == deposit index), chunked like any batchable request
+// (plan_batch: chunkifyMaximizeChunkSize at 16).  The batch carries the signatures only:
+// the pass's front kernel makes each request's key and signing root on the device from the
+// deposit's fields, so there is nothing to dedup and no key list.
+struct DepositPlan {
+  std::vector<uint32_t> off;       // n + 1: 0, 1, .., n (request r owns set r)
+  std::vector<uint8_t> batchable;  // n ones
+};
+
+// shape checks of the caller's batch: nullptr, or what is wrong (the call returns -2)
+inline const char* check_deposits(const bls_deposit_batch* in, const int32_t* verdicts) {
+  if (in->n > BLS_DEPOSITS_MAX_CALL) return "more than BLS_DEPOSITS_MAX_CALL deposits";
+  if (!in->pubkeys48 || !in->withdrawal_credentials || !in->amounts || !in->signatures || !in->domain || !verdicts)
+    return "a required pointer is NULL";
+  return nullptr;
+}
+
+// fills p and points `all` at it (p must outlive the pass)
+inline void plan_deposits(const bls_deposit_batch* in, DepositPlan& p, bls_batch& all) {
+  const uint32_t n = in->n;
+  p.off.resize((size_t)n + 1);
+  for (uint32_t i = 0; i <= n; ++i) p.off[i] = i;
+  p.batchable.assign(n, 1);
+  memset(&all, 0, sizeof(all));
+  all.n_sets = n;
+  all.n_reqs = n;
+  all.req_set_offsets = p.off.data();
+  all.req_batchable = p.batchable.data();
+  all.signatures = in->signatures;
+  all.seed = in->seed;
+}
+
 // Signing-root dedup for stage_pre: uniq = the first set of each distinct 32-byte
 // root (in set order), rep[i] = that first set for set i.  Committee-shared roots
 // (~512 attesters per root) then pay hash_to_field + SSWU once.

@@ -3,12 +3,14 @@
 // single-lane bodies in bls/pipeline.hpp, host-side plans in bls/plan.hpp (both shared with
 // the CPU test harness); cooperative programs from tools/gen_coop.py.
 //
-// Every verify entry point (bls_gpu_verify, _verify_many, _verify_same_message, _partial)
-// is one VerifyPass (below): plan_pass fixes its shape and plans, then verify_body calls
+// Every verify entry point (bls_gpu_verify, _verify_many, _verify_same_message, _partial,
+// _verify_deposits) is one VerifyPass (below): plan_pass fixes its shape and plans, then verify_body calls
 // its stages in order.  The inputs sit in pinned mapped staging memory (no H2D copy), all
 // kernels run on the context's stream, and the host waits after the first pass and after
 // each fallback round.
 //   k_pk, k_pre   pubkey decode / table aggregation; SSWU points of H(m), signature decode
+//                 (a deposit call: k_deposit in k_pk's place -- KeyValidate of the
+//                 compressed keys and the signing roots, made on the device)
 //   first pass, one of two shapes (use_sigagg):
 //     per set     k_pset (k_psetn: up to 3 sets per wavefront): H(m), G2 subgroup test,
 //                 r pk, r g1, f_i = ML(r pk, H) ML(-r g1, sig), one wavefront per set
@@ -49,6 +51,7 @@
 #include <string>
 #include <vector>
 
+#include "bls/deposit.hpp"
 #include "bls/group_decode.hpp"
 #include "bls/plan.hpp"
 #include "launchers.hpp"
@@ -925,12 +928,16 @@ struct PassArgs {
   uint32_t* partial_err;
   const std::vector<uint32_t>* req_bounds;  // verify_many: the messages' first requests
   const SameMsgPlan* sm;                    // verify_same_message: its own plan
+  // verify_deposits: the caller's arrays.  The batch of such a pass is n one-set batchable
+  // requests with neither keys nor messages on the host: k_deposit makes both
+  const bls_deposit_batch* dep;
 };
 
 // Every decision and count of a pass, fixed by plan_pass before anything is staged.
 struct PassShape {
   uint32_t n, R, n_chunks, n_uniq, n_pk_idx;
   bool partial, sm, dedup;
+  bool dep;  // a deposit call (PassArgs::dep)
   // Merged check: with only batchable requests and >= 2 chunks, first test the product of
   // every f_i with ONE final exponentiation (k_fprod tree); it passes iff every chunk would
   // (the same random-scalar batch, just larger), so chunk_ok is all 1 and the per-chunk
@@ -1000,6 +1007,7 @@ PassShape plan_pass(const bls_gpu_ctx* ctx, const bls_batch* in, const PassArgs&
   const uint32_t* req_off = in->req_set_offsets;
   sh.partial = a.partial_out != nullptr;
   sh.sm = a.sm != nullptr;
+  sh.dep = a.dep != nullptr;
   if (a.sm) {
     pl.plan = &a.sm->plan;  // every job a caller-defined chunk (plan_same_message)
   } else {
@@ -1008,12 +1016,15 @@ PassShape plan_pass(const bls_gpu_ctx* ctx, const bls_batch* in, const PassArgs&
     pl.plan = &pl.built;
   }
   const BatchPlan& plan = *pl.plan;
-  sh.n_uniq = (flags & BLS_DEBUG_NO_MSG_DEDUP) ? n : plan_msg_dedup(in->messages, n, pl.msg_uniq, pl.msg_rep);
+  // (a deposit call's roots are made on the device: nothing to dedup on the host)
+  const bool no_dedup = sh.dep || (flags & BLS_DEBUG_NO_MSG_DEDUP);
+  sh.n_uniq = no_dedup ? n : plan_msg_dedup(in->messages, n, pl.msg_uniq, pl.msg_rep);
   sh.dedup = sh.n_uniq < n;
-  sh.merged_after_fail = ctx->last_merged_failed;
+  // (same-message and deposit calls neither read nor write the context's merged-check
+  // history: invalid deposits are normal and must not shape the next gossip pass)
+  sh.merged_after_fail = !sh.dep && ctx->last_merged_failed;
   sh.merged_eligible = !sh.partial && plan.chunk_off.size() > 2 && plan.nonbatch_reqs.empty() && n > 0 &&
                        !(flags & BLS_DEBUG_NO_MERGED_CHECK);
-  // (same-message calls neither read nor write the context's merged-check history)
   sh.merged_skipped = sh.merged_eligible && !sh.sm && sh.merged_after_fail && merged_skip_after_fail() &&
                       !(flags & BLS_DEBUG_MERGED_EVERY_PASS);
   sh.merged = sh.merged_eligible && !sh.merged_skipped;
@@ -1079,6 +1090,7 @@ struct VerifyPass {
   PipeBufs b;
   GroupBufs g;
   MsmBufs msm;
+  DepositBufs dep;
   size_t input_end = 0;                  // [0, input_end) of the carve is the mapped staging area
   Fp12* ptree[2] = {nullptr, nullptr};   // product-tree levels (partial mode, merged check)
   int32_t* merged_ok = nullptr;          // FE(prod f_i) == 1 of the merged check
@@ -1111,6 +1123,7 @@ struct VerifyPass {
     memset(&b, 0, sizeof(b));
     memset(&g, 0, sizeof(g));
     memset(&msm, 0, sizeof(msm));
+    memset(&dep, 0, sizeof(dep));
   }
 
   // ---- workspace: inputs first (they live in the mapped staging area), then intermediates.
@@ -1122,11 +1135,17 @@ struct VerifyPass {
     b.chunk_off = c.take<uint32_t>(n_chunks + 1);
     b.chunk_reqs = c.take<uint32_t>(plan.chunk_reqs.size());
     b.seed = c.take<uint32_t>(8);
-    b.pubkeys = in->set_pk_offsets ? nullptr : c.take<uint8_t>(96ull * n);
+    b.pubkeys = in->set_pk_offsets || sh.dep ? nullptr : c.take<uint8_t>(96ull * n);
     b.set_pk_off = in->set_pk_offsets ? c.take<uint32_t>(n + 1) : nullptr;
     b.pk_idx = in->set_pk_offsets ? c.take<uint32_t>(sh.n_pk_idx) : nullptr;
     b.agg_sets = pl.agg_list.empty() ? nullptr : c.take<uint32_t>(pl.agg_list.size());
-    b.msgs = c.take<uint8_t>(32ull * n);
+    b.msgs = sh.dep ? nullptr : c.take<uint8_t>(32ull * n);  // (a deposit call: device memory, below)
+    if (sh.dep) {
+      dep.pubkeys48 = c.take<uint8_t>(48ull * n);
+      dep.wc = c.take<uint8_t>(32ull * n);
+      dep.amounts = c.take<uint8_t>(8ull * n);
+      dep.domain = c.take<uint8_t>(32);
+    }
     b.msg_uniq = sh.dedup ? c.take<uint32_t>(sh.n_uniq) : nullptr;
     b.msg_rep = sh.dedup ? c.take<uint32_t>(n) : nullptr;
     b.sigs = c.take<uint8_t>(96ull * n);
@@ -1149,6 +1168,7 @@ struct VerifyPass {
       useg_dev = sh.smsum ? nullptr : c.take<uint32_t>(pl.unit_gsum.seg.size());
     }
     input_end = c.off;
+    if (sh.dep) b.msgs = dep.roots = c.take<uint8_t>(32ull * n);  // written by k_deposit
     b.sig = c.take<G2A>(n);
     b.sig_status = c.take<int32_t>(n);
     b.pk = c.take<G1J>(n);
@@ -1260,7 +1280,14 @@ struct VerifyPass {
       stage_copy(ctx, b.set_pk_off, in->set_pk_offsets, sizeof(uint32_t) * (n + 1));
       stage_copy(ctx, b.pk_idx, in->pk_indices, sizeof(uint32_t) * sh.n_pk_idx);
     }
-    stage_copy(ctx, b.msgs, in->messages, 32ull * n);
+    if (sh.dep) {
+      stage_copy(ctx, dep.pubkeys48, a.dep->pubkeys48, 48ull * n);
+      stage_copy(ctx, dep.wc, a.dep->withdrawal_credentials, 32ull * n);
+      stage_copy(ctx, dep.amounts, a.dep->amounts, 8ull * n);
+      stage_copy(ctx, dep.domain, a.dep->domain, 32);
+    } else {
+      stage_copy(ctx, b.msgs, in->messages, 32ull * n);
+    }
     if (in->signature_lens) {
       // bytes past a short signature's length are never read (the set fails INVALID_SIZE)
       for (uint32_t i = 0; i < n; ++i) {
@@ -1334,8 +1361,13 @@ struct VerifyPass {
       for (int i = 1; i <= 5; ++i) HIPC(ctx, hipEventRecord(ctx->ev[i], s));
       return 0;
     }
-    HIPC(ctx, launch_k_pk(b, s));  // also resets set_flag, flag_count, the next first_bad_pk slot
-    HIPC(ctx, launch_k_pk_agg(b, s)); dbg_sync(s, "k_pk");
+    // either also resets set_flag, flag_count, the next first_bad_pk slot
+    if (sh.dep) {
+      HIPC(ctx, launch_k_deposit(b, dep, s)); dbg_sync(s, "k_deposit");
+    } else {
+      HIPC(ctx, launch_k_pk(b, s));
+      HIPC(ctx, launch_k_pk_agg(b, s)); dbg_sync(s, "k_pk");
+    }
     ctx->first_bad_slot ^= 1u;
     HIPC(ctx, hipEventRecord(ctx->ev[1], s));
     HIPC(ctx, launch_k_pre(b, s)); dbg_sync(s, "k_pre");
@@ -1465,7 +1497,7 @@ struct VerifyPass {
     const uint32_t n_chunks = sh.n_chunks;
     merged_pass = sh.merged && merged_verdict == 1;
     for (uint32_t r = 0; merged_pass && r < sh.R; ++r) merged_pass = merged_status[r] == BLS_OK;
-    if (sh.merged && !sh.sm) ctx->last_merged_failed = !merged_pass;
+    if (sh.merged && !sh.sm && !sh.dep) ctx->last_merged_failed = !merged_pass;
     if (merged_pass) {
       for (uint32_t ch = 0; ch < n_chunks; ++ch) chunk_ok[ch] = 1;
     } else if (n_chunks > 0 && !sh.partial) {
@@ -1830,7 +1862,9 @@ int verify_body(bls_gpu_ctx* ctx, const bls_batch* in, const PassArgs& a) {
   HIPC(ctx, hipSetDevice(ctx->device));
   if (a.stats) memset(a.stats, 0, sizeof(*a.stats));
   if (in->n_reqs == 0) return 0;
-  if (const int rc = check_batch(in, "batch", ctx->err, sizeof(ctx->err))) return rc;
+  // (a deposit call built its batch itself, with neither keys nor messages on the host)
+  if (!a.dep)
+    if (const int rc = check_batch(in, "batch", ctx->err, sizeof(ctx->err))) return rc;
   const InFlight in_flight(in->n_sets);
   VerifyPass p(ctx, in, a);
   int rc;
@@ -1854,11 +1888,11 @@ int verify_body(bls_gpu_ctx* ctx, const bls_batch* in, const PassArgs& a) {
 static int verify_impl(bls_gpu_ctx* ctx, const bls_batch* in, int32_t* verdicts, bls_stats* stats,
                        uint32_t scalar_base, uint8_t* partial_out, int32_t* partial_status,
                        uint32_t* partial_err = nullptr, const std::vector<uint32_t>* req_bounds = nullptr,
-                       const SameMsgPlan* sm = nullptr) {
+                       const SameMsgPlan* sm = nullptr, const bls_deposit_batch* dep = nullptr) {
   CTX_LOCK(ctx);
   ctx->wait_block = wait_blocks(in->n_sets);
   const int rc = verify_body(ctx, in, PassArgs{verdicts, stats, scalar_base, partial_out, partial_status, partial_err,
-                                               req_bounds, sm});
+                                               req_bounds, sm, dep});
   if (rc < 0 && ctx->msm_state) {
     (void)hipStreamSynchronize(ctx->stream);
     (void)hipMemsetAsync(ctx->msm_state, 0, sizeof(uint32_t) * MSM_STATE_WORDS, ctx->stream);
@@ -1993,6 +2027,25 @@ int bls_gpu_verify_same_message(bls_gpu_ctx* ctx, const bls_same_msg_batch* in, 
   all.signatures = in->signatures;
   all.seed = in->seed;
   return verify_impl(ctx, &all, set_verdicts, stats, 0u, nullptr, nullptr, nullptr, nullptr, &sm);
+}
+
+int bls_gpu_verify_deposits(bls_gpu_ctx* ctx, const bls_deposit_batch* in, int32_t* verdicts, bls_stats* stats) {
+  if (!ctx || !in) return -2;
+  const uint32_t n = in->n;
+  if (n == 0) return 0;  // (nothing written, stats neither)
+  if (stats) memset(stats, 0, sizeof(*stats));
+  if (const char* what = check_deposits(in, verdicts)) {
+    CTX_LOCK(ctx);
+    snprintf(ctx->err, sizeof(ctx->err), "deposit batch: %s", what);
+    return -2;
+  }
+  // the call as n one-set batchable requests (bls/plan.hpp plan_deposits); the front kernel
+  // makes each one's key and signing root from the deposit's fields (PassArgs::dep), the
+  // table is not consulted
+  DepositPlan dp;
+  bls_batch all;
+  plan_deposits(in, dp, all);
+  return verify_impl(ctx, &all, verdicts, stats, 0u, nullptr, nullptr, nullptr, nullptr, nullptr, in);
 }
 
 int bls_gpu_partial(bls_gpu_ctx* ctx, const bls_batch* in, uint32_t set_index_base, uint8_t* out576,

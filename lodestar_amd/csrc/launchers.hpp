@@ -24,6 +24,11 @@ hipError_t launch_k_load_pubkeys(const uint8_t* pks, uint32_t n, uint32_t pk_len
                                  hipStream_t s);
 hipError_t launch_k_status(const bls::PipeBufs& b, hipStream_t s);
 hipError_t launch_k_validate_pubkeys(const uint8_t* pks, uint32_t n, uint32_t pk_len, int32_t* codes, hipStream_t s);
+// the front kernel of a deposit call, in k_pk's place (kernels/k_deposit.hip, bls/deposit.hpp)
+namespace bls {
+struct DepositBufs;
+}
+hipError_t launch_k_deposit(const bls::PipeBufs& b, const bls::DepositBufs& d, hipStream_t s);
 hipError_t launch_k_pre(const bls::PipeBufs& b, hipStream_t s);
 hipError_t launch_k_exact(const bls::PipeBufs& b, hipStream_t s);
 // roles: bit k runs k_chain role k (0 H, 1 subgroup, 2 [r] sig, 3 [r] pk); k_chain_done

@@ -12,7 +12,7 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from ._abi import ERR_ADMISSION, BlsAdmission, BlsBatch, BlsSameMsgBatch, BlsStats, load_library
+from ._abi import ERR_ADMISSION, BlsAdmission, BlsBatch, BlsDepositBatch, BlsSameMsgBatch, BlsStats, load_library
 
 
 def _ptr(a: np.ndarray | None):
@@ -212,6 +212,48 @@ def pack_same_message(jobs, seed: bytes | None = None) -> PackedSameMsg:
     )
 
 
+@dataclass
+class PackedDeposits:
+    """SoA form of one bls_gpu_verify_deposits call (bls_deposit_batch)."""
+
+    pubkeys48: np.ndarray  # uint8[n * 48]
+    withdrawal_credentials: np.ndarray  # uint8[n * 32]
+    amounts: np.ndarray  # uint8[n * 8], little-endian Gwei
+    signatures: np.ndarray  # uint8[n * 96]
+    domain: np.ndarray  # uint8[32]
+    n: int = 0
+    seed: bytes | None = None
+
+
+def pack_deposits(deposits, domain: bytes, seed: bytes | None = None) -> PackedDeposits:
+    """deposits: list of (pubkey48, withdrawal_credentials32, amount: int, signature96), the
+    fields of a DepositData; domain: the call's 32-byte deposit domain."""
+    if len(domain) != 32:
+        raise ValueError("the deposit domain is 32 bytes")
+    pks, wcs, amts, sigs = [], [], [], []
+    for pk, wc, amount, sig in deposits:
+        pk, wc, sig = bytes(pk), bytes(wc), bytes(sig)
+        if len(pk) != 48:
+            raise ValueError(f"deposit pubkeys are 48 bytes (compressed G1), got {len(pk)}")
+        if len(wc) != 32:
+            raise ValueError(f"withdrawal credentials are 32 bytes, got {len(wc)}")
+        if len(sig) != 96:
+            raise ValueError(f"deposit signatures are 96 bytes (compressed G2), got {len(sig)}")
+        amount = int(amount)
+        if not 0 <= amount < 1 << 64:
+            raise ValueError(f"a deposit amount is a uint64 (Gwei), got {amount}")
+        pks.append(pk)
+        wcs.append(wc)
+        amts.append(amount.to_bytes(8, "little"))
+        sigs.append(sig)
+
+    def join(parts, size):
+        return np.frombuffer(b"".join(parts), dtype=np.uint8).copy() if parts else np.zeros(size, np.uint8)
+
+    return PackedDeposits(pubkeys48=join(pks, 48), withdrawal_credentials=join(wcs, 32), amounts=join(amts, 8),
+                          signatures=join(sigs, 96), domain=_u8(domain), n=len(pks), seed=seed)
+
+
 class GpuContext:
     def __init__(self, device: int = 0, high_priority: bool = False):
         """high_priority: the context's stream outranks normal contexts' queued kernels
@@ -343,6 +385,22 @@ class GpuContext:
         self._check(rc, "bls_gpu_verify_same_message")
         off = ps.job_set_offsets
         return [verdicts[int(off[j]): int(off[j + 1])] for j in range(ps.n_jobs)], stats
+
+    def verify_deposits_packed(self, pd: PackedDeposits) -> tuple[int, np.ndarray, BlsStats]:
+        """bls_gpu_verify_deposits as it is: (return code, n verdicts 1 / 0 / -code, stats)."""
+        b = BlsDepositBatch()
+        b.n = pd.n
+        keep = [np.ascontiguousarray(getattr(pd, f)) for f in ("pubkeys48", "withdrawal_credentials", "amounts",
+                                                                "signatures", "domain")]
+        b.pubkeys48, b.withdrawal_credentials, b.amounts, b.signatures, b.domain = (_ptr(a) for a in keep)
+        seed_buf = None
+        if pd.seed is not None:
+            seed_buf = ctypes.create_string_buffer(bytes(pd.seed), 32)
+            b.seed = ctypes.cast(seed_buf, ctypes.c_void_p)
+        verdicts = np.zeros(max(pd.n, 1), dtype=np.int32)
+        stats = BlsStats()
+        rc = self.lib.bls_gpu_verify_deposits(self._h, ctypes.byref(b), _ptr(verdicts), ctypes.byref(stats))
+        return rc, verdicts[: pd.n], stats
 
     def partial(self, pb: PackedBatch, set_index_base: int):
         """Miller-loop partial of this shard of a sharded call (bls_gpu_partial):

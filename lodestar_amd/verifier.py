@@ -42,6 +42,13 @@ with GPU contexts in place of worker threads:
   throwing set).  Sets whose key is not a table index (raw bytes, an index list) do not
   enter the batch: each goes through the existing path as a one-set batchable request.
 
+* `verify_deposits(deposits, fork_version)` (processDeposit.ts:48-65, outside
+  IBlsVerifier): one bool per deposit through bls_gpu_verify_deposits
+  (lodestar_amd/deposits.py).  Each call, or each part of at most BLS_DEPOSITS_MAX_CALL
+  deposits, is its own job kind: an idle context of the least-loaded slot takes one part
+  per native call, a deposit weighing one set.  An invalid deposit is False, never an
+  exception; the device tables are not touched.
+
 * several devices (`devices=[0, 1, ...]`, one verifier per node): the reference's pool
   spreads one call's 128-set jobs over every worker of the process (index.ts:153-166,
   199-233, poolSize.ts:3-11); here every device slot opens `n_contexts` contexts with
@@ -136,6 +143,15 @@ class _SameMsgJob:
     added: float
 
 
+@dataclass
+class _DepositJob:
+    """One part (<= BLS_DEPOSITS_MAX_CALL deposits) of a verify_deposits call."""
+
+    packed: object  # native.PackedDeposits
+    future: Future
+    added: float
+
+
 def set_weight(pk) -> float:
     """Routing weight of one set: 1 for a single key, 1 + k / AGG_KEY_WEIGHT for an
     aggregate of k table keys (a G1 addition is ~11 of a set's ~12.7k Fp products, so
@@ -202,6 +218,7 @@ class GpuBlsVerifier:
         self._cv = threading.Condition()
         self._jobs: list[_Job] = []
         self._sm_jobs: list[_SameMsgJob] = []
+        self._dep_jobs: list[_DepositJob] = []
         self._buffer: list[_Job] = []
         self._buffer_sigs = 0
         self._buffer_first = 0.0
@@ -341,6 +358,60 @@ class GpuBlsVerifier:
             f.add_done_callback(lambda f, positions=positions, single=single: part_done(positions, f, single))
         return out
 
+    def verify_deposits(self, deposits, fork_version: bytes | None = None, domain: bytes | None = None) -> list[bool]:
+        return self.verify_deposits_async(deposits, fork_version, domain).result()
+
+    def verify_deposits_async(self, deposits, fork_version: bytes | None = None,
+                              domain: bytes | None = None) -> Future:
+        """Deposits `(pubkey48, withdrawal_credentials32, amount, signature96)` checked as
+        processDeposit checks them (lodestar_amd/deposits.py): the future resolves to one
+        bool per deposit.  Parts of at most BLS_DEPOSITS_MAX_CALL deposits are queued as
+        jobs of their own and routed like every other job, to the least-loaded slot."""
+        from .deposits import deposit_domain, screen_deposits, split_deposits
+        from .native import pack_deposits
+
+        if (fork_version is None) == (domain is None):
+            raise ValueError("give fork_version or domain")
+        dom = bytes(domain) if domain is not None else deposit_domain(fork_version)
+        deposits = list(deposits)
+        out: Future = Future()
+        taken, pos = screen_deposits(deposits)
+        results = [False] * len(deposits)  # (a signature of the wrong length stays False)
+        parts = split_deposits(taken)
+        if not parts:
+            out.set_result(results)
+            return out
+        if not self._ctxs and self.init_errors:
+            raise self.init_errors[0]
+        jobs = [_DepositJob(pack_deposits(part, dom), Future(), time.monotonic()) for part in parts]
+        lock = threading.Lock()
+        pending = [len(jobs)]
+
+        def part_done(first, f):
+            with lock:
+                if out.done():
+                    return
+                if f.exception() is not None:
+                    out.set_exception(f.exception())
+                    return
+                for k, code in enumerate(f.result()):
+                    results[pos[first + k]] = int(code) == 1
+                pending[0] -= 1
+                if pending[0] == 0:
+                    out.set_result(results)
+
+        with self._cv:
+            if self._closed:
+                out.set_exception(QueueAborted("QUEUE_ABORTED"))
+                return out
+            self._dep_jobs.extend(jobs)
+            self._cv.notify_all()
+        first = 0
+        for j in jobs:
+            j.future.add_done_callback(lambda f, first=first: part_done(first, f))
+            first += j.packed.n
+        return out
+
     def _queue_call(self, sets: list, batchable: bool) -> Future:
         """The reference's path: chunkifyMaximizeChunkSize(sets, 128) jobs, AND-ed."""
         jobs = [self._queue(chunk, batchable) for chunk in chunkify_maximize_chunk_size(sets, MAX_SIGNATURE_SETS_PER_JOB)]
@@ -434,9 +505,9 @@ class GpuBlsVerifier:
     def close(self) -> None:
         with self._cv:
             self._closed = True
-            pending = self._jobs + self._buffer + self._sm_jobs
+            pending = self._jobs + self._buffer + self._sm_jobs + self._dep_jobs
             pinned = [p for lst in self._pinned for p in lst]
-            self._jobs, self._buffer, self._sm_jobs = [], [], []
+            self._jobs, self._buffer, self._sm_jobs, self._dep_jobs = [], [], [], []
             self._pinned = [[] for _ in self._pinned]
             self._cv.notify_all()
         for j in pending:
@@ -582,7 +653,7 @@ class GpuBlsVerifier:
     def _worker(self, ctx, slot: int, wid: int):
         tp = self.metrics.blsThreadPool
         while True:
-            pin, jobs, sm_jobs = None, None, None
+            pin, jobs, sm_jobs, dep_job = None, None, None, None
             with self._cv:
                 self._idle[slot] += 1
                 while True:
@@ -596,6 +667,9 @@ class GpuBlsVerifier:
                         sm_jobs = self._prepare_same_message_work()
                         if sm_jobs:
                             break
+                    if self._dep_jobs and self._my_turn(slot):
+                        dep_job = self._dep_jobs.pop(0)
+                        break
                     if self._jobs and self._my_turn(slot):
                         jobs = self._prepare_work()
                         if jobs:
@@ -604,6 +678,8 @@ class GpuBlsVerifier:
                 self._idle[slot] -= 1
                 if sm_jobs is not None:
                     keys = [i for j in sm_jobs for i in j.indices]
+                elif dep_job is not None:
+                    keys = [0] * dep_job.packed.n  # one key per deposit: each weighs one set
                 else:
                     keys = [pk for pk, _, _ in (pin.sets if pin is not None else [s for j in jobs for s in j.sets])]
                 weight = sum(set_weight(pk) for pk in keys)
@@ -617,6 +693,8 @@ class GpuBlsVerifier:
                     self._run_pinned(ctx, pin)
                 elif sm_jobs is not None:
                     self._run_same_message_jobs(ctx, sm_jobs, wid, tp)
+                elif dep_job is not None:
+                    self._run_deposit_job(ctx, dep_job, wid, tp)
                 else:
                     self._run_jobs(ctx, jobs, wid, tp)
             finally:
@@ -658,6 +736,29 @@ class GpuBlsVerifier:
         for j, v in zip(jobs, verdicts):
             j.future.set_result([int(x) for x in v])
             tp.successJobsSignatureSetsCount.inc(len(j.indices))
+
+    def _run_deposit_job(self, ctx, job, wid, tp):
+        """one bls_gpu_verify_deposits call; the job's future resolves to its deposits' codes"""
+        n = job.packed.n
+        tp.jobWaitTime.observe(time.monotonic() - job.added)
+        tp.totalJobsGroupsStarted.inc(1)
+        tp.totalJobsStarted.inc(1)
+        tp.totalSigSetsStarted.inc(n)
+        try:
+            t0 = time.perf_counter()
+            rc, verdicts, stats = ctx.verify_deposits_packed(job.packed)
+            ctx._check(rc, "bls_gpu_verify_deposits")
+            t1 = time.perf_counter()
+        except Exception as e:  # noqa: BLE001 - a runtime failure rejects the call
+            job.future.set_exception(e)
+            tp.errorJobsSignatureSetsCount.inc(n)
+            return
+        tp.jobsWorkerTime.inc({"workerId": wid}, stats.device_ms / 1e3)
+        tp.latencyFromWorker.observe(max(0.0, (t1 - t0) - stats.device_ms / 1e3))
+        tp.batchRetries.inc(stats.batch_retries)
+        tp.batchSigsSuccess.inc(stats.batch_sigs_success)
+        job.future.set_result([int(x) for x in verdicts])
+        tp.successJobsSignatureSetsCount.inc(n)
 
     def _run_jobs(self, ctx, jobs, wid, tp):
         if self.call_log is not None:
