@@ -163,7 +163,11 @@ const char* bls_gpu_last_error(const bls_gpu_ctx* ctx);
  * (uncompressed).  codes (nullable, n entries) receive a per-key decode code; keys
  * are not subgroup-checked (trusted, pubkeyCache.ts:72-75).  All or nothing: when any
  * key fails to decode, no key is appended (the table keeps its size, so indices stay
- * aligned across contexts).  Returns the new table size (>= 0) or < 0 on failure. */
+ * aligned across contexts).  Returns the new table size (>= 0) or < 0 on failure.
+ * Beside the 100 B table entry the load builds 1,440 B of comb rows per key (15 affine
+ * multiples; [r] pk of a single-key set runs on them), up to $BLS_PK_COMB_MAX_MB MiB per
+ * context (default 4096; keys past it, or every key if that memory cannot be had, verify
+ * through the per-set chain as before; $BLS_PK_COMB=0: no rows). */
 int64_t bls_gpu_load_pubkeys(bls_gpu_ctx* ctx, const uint8_t* pks, uint32_t n, uint32_t pk_len, int32_t* codes);
 
 /* KeyValidate for n public keys (blst PublicKey.fromBytes(bytes, validate=true) [ext],
@@ -444,6 +448,10 @@ int bls_gpu_kernel_probe(bls_gpu_ctx* ctx, const char* name, uint32_t lanes, uin
 /* Test hook: run the merged check on every pass, also after a pass that failed it (by
  * default such a context's next pass checks its chunks straight away, merged_check 3). */
 #define BLS_DEBUG_MERGED_EVERY_PASS 0x8000u
+/* Test / bench hook: [r] pk by the GLV chain for every set of this context, also where the
+ * key's comb rows exist (bls_gpu_load_pubkeys builds them; $BLS_PK_COMB=0 turns them off
+ * for the process), so one process can run the same call through both. */
+#define BLS_DEBUG_NO_PK_COMB 0x10000u
 int bls_gpu_set_debug_flags(bls_gpu_ctx* ctx, uint32_t flags);
 
 #ifdef __cplusplus

@@ -97,6 +97,7 @@ DEBUG_NO_UNITS = 32
 DEBUG_MSM = 64
 DEBUG_GROUP_TEST = 128
 DEBUG_MERGED_EVERY_PASS = 0x8000  # (bits 8-9 are BLS_DEBUG_PACK, 12-14 BLS_DEBUG_MLF_PL)
+DEBUG_NO_PK_COMB = 0x10000  # [r] pk by the GLV chain also where the key has comb rows
 
 
 def DEBUG_MLF_PL(n: int) -> int:

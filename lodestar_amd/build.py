@@ -305,6 +305,13 @@ def build_deposit_host(verbose: bool = True, out: Path | None = None, extra: lis
     return _build_host_program("deposit_host", (), verbose, out, extra)
 
 
+def build_comb_host(verbose: bool = True, out: Path | None = None, extra: list[str] | None = None) -> Path:
+    """The pubkey table's fixed-base comb (bls/curve.hpp g1_comb_build / g1_comb_mul) against
+    the GLV chain, and on records from a file (tests/native/comb_host.cpp), a stand-alone
+    program for tests/; `extra` as above."""
+    return _build_host_program("comb_host", (), verbose, out, extra)
+
+
 def build_cpu_baseline(verbose: bool = True) -> Path:
     """The C++ CPU baseline under oracle/cpu (benchmark / test infrastructure, "not
     blst"; oracle/cpu/bls_cpu.cpp), next to its source: bench.py's cpu_baseline leg
@@ -348,4 +355,5 @@ if __name__ == "__main__":
     build_smsum_host()
     build_plan_host()
     build_deposit_host()
+    build_comb_host()
     build_cpu_baseline()

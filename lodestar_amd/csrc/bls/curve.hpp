@@ -394,6 +394,88 @@ BLS_HD void glv_split(uint64_t r64, uint32_t& a, uint32_t& b) {
   b = (uint32_t)(r64 >> 32);
 }
 
+// ---- fixed-base comb for [a]P + [b]sigma(P) on a G1 point that stays the same ------
+// A key of the device pubkey table does not change from call to call, so the multiples
+// the batch scalar needs are made once, at load time.  Per key 15 affine rows (x, y;
+// G1_COMB_WORDS Fp, one key's rows contiguous):
+//   C[k] = sum_{t=0..3} bit_t(k) [2^(8t)] P,   k = 1..15   (C[k] at rows[2 (k - 1)])
+// With a = sum a_t 2^(8t) (a_t the bytes of a) and b likewise, column j = 7..0 of the four
+// bytes is one row index, so [a]P + [b]sigma(P) is 7 doublings and 16 mixed additions
+// (sigma(x, y) = (beta x, y) on a row: one product), whatever a and b: no per-set table.
+// The comb only regroups [a]P + [b]sigma(P) and sigma is an endomorphism of the whole
+// curve, so with the complete formulas it is the group element jac_mul_glv gives for
+// every on-curve P, inside G1 or not.
+enum : int { G1_COMB_ROWS = 15, G1_COMB_WORDS = 30 };
+
+// bit j of each of the four bytes of v, as a row index 0..15
+BLS_HD uint32_t g1_comb_digit(uint32_t v, int j) {
+  return ((v >> j) & 1u) | (((v >> (8 + j)) & 1u) << 1) | (((v >> (16 + j)) & 1u) << 2) |
+         (((v >> (24 + j)) & 1u) << 3);
+}
+
+// One rolled loop over the 16 (column, half) steps: a single copy of the mixed addition.
+BLS_HD G1J g1_comb_mul(const Fp* rows, uint32_t a, uint32_t b) {
+  G1J acc = jac_infinity<Fp>();
+#pragma unroll 1
+  for (int s = 15; s >= 0; --s) {
+    const bool endo = !(s & 1);  // a column's a digit first (odd s), then its b digit
+    if (!endo && !jac_is_inf(acc)) acc = jac_dbl(acc);
+    const uint32_t k = g1_comb_digit(endo ? b : a, s >> 1);
+    if (k) {
+      G1A q;
+      q.x = rows[2 * (k - 1)];
+      q.y = rows[2 * (k - 1) + 1];
+      q.inf = false;
+      if (endo) q.x = fp_mul(q.x, c_g1_beta());
+      acc = jac_add_aff(acc, q);
+    }
+  }
+  return acc;
+}
+
+// The rows of one key: 24 doublings, 11 additions, then every entry made affine with one
+// shared inversion (Montgomery's trick).  T: 15 Jacobian entries of caller-provided
+// memory (the entries before they are affine: 2,160 B, kept out of the private frame);
+// the running products of the Z's pass through rows itself (entry k's affine form lands
+// at rows[2k], rows[2k + 1], above the products 0..k-1 still to be read).  False: no comb
+// for this key -- it is infinity, or an entry is (a key of small order, outside G1);
+// rows then hold nothing of use.
+BLS_HD bool g1_comb_build(const G1A& p, G1J* T, Fp* rows) {
+  if (p.inf) return false;
+  G1J t = jac_from_aff(p);
+  T[0] = t;
+#pragma unroll 1
+  for (int w = 1; w < 4; ++w) {
+#pragma unroll 1
+    for (int i = 0; i < 8; ++i) t = jac_dbl(t);
+    T[(1 << w) - 1] = t;  // [2^(8w)] P
+  }
+#pragma unroll 1
+  for (uint32_t k = 3; k < 16; ++k) {
+    const uint32_t low = k & (0u - k);
+    if (low != k) T[k - 1] = jac_add(T[(k ^ low) - 1], T[low - 1]);
+  }
+  Fp run = T[0].z;
+  rows[0] = run;
+#pragma unroll 1
+  for (int k = 1; k < G1_COMB_ROWS; ++k) {
+    run = fp_mul(run, T[k].z);
+    rows[k] = run;  // z_0 .. z_k
+  }
+  if (fp_is_zero(run)) return false;  // some entry at infinity
+  Fp inv = fp_inv_gcd(run);
+#pragma unroll 1
+  for (int k = G1_COMB_ROWS - 1; k >= 0; --k) {
+    const G1J e = T[k];
+    const Fp zi = k ? fp_mul(inv, rows[k - 1]) : inv;
+    if (k) inv = fp_mul(inv, e.z);
+    const Fp zi2 = fp_sqr(zi);
+    rows[2 * k] = fp_mul(e.x, zi2);
+    rows[2 * k + 1] = fp_mul(e.y, fp_mul(zi2, zi));
+  }
+  return true;
+}
+
 // ---- serialization (ZCash format) ---------------------------------------------
 // Error codes follow blst's BLST_ERROR enum; values >= 8 are Lodestar/chainsafe-level.
 enum BlsCode : int32_t {

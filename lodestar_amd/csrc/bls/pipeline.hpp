@@ -46,6 +46,13 @@ struct PipeBufs {
   const uint32_t* pk_idx;
   const G1A* pk_table;
   uint32_t pk_table_n;
+  // fixed-base comb rows of the table's keys (curve.hpp g1_comb_mul): G1_COMB_WORDS Fp per
+  // key for keys [0, pk_comb_n), pk_comb_ok[idx] = 1 where the key has rows; nullptr: no
+  // comb (off, or the allocation failed) and every set takes the GLV chain
+  const Fp* pk_comb;
+  const uint8_t* pk_comb_ok;
+  uint32_t pk_comb_n;
+  const Fp* g1_comb;  // the generator's rows (the per-set path's RG = [s] g1), nullable
   // aggregate sets of >= agg_min keys (0: none) are summed one wavefront per set by
   // k_pk_agg (a lane per key stride, then a tree over the lanes); stage_pk skips them
   const uint32_t* agg_sets;    // n_agg set indices
@@ -209,6 +216,18 @@ BLS_HD void stage_pk(const PipeBufs& b, uint32_t i) {
   b.pk[i] = acc;
   b.pk_status[i] = code;
   if (b.pk_inf) b.pk_inf[i] = (code == BLS_OK && jac_is_inf(acc)) ? 1 : 0;
+}
+
+// The comb rows [r] pk of set i may use, or nullptr (the GLV chain on b.pk[i]): the set
+// has exactly one table key, and that key has rows.  (Plain pointers: see k_chain's roles.)
+BLS_HD const Fp* set_comb_rows(const uint32_t* set_pk_off, const uint32_t* pk_idx, const Fp* comb,
+                               const uint8_t* comb_ok, uint32_t comb_n, uint32_t i) {
+  if (!comb || !set_pk_off) return nullptr;
+  const uint32_t beg = set_pk_off[i];
+  if (set_pk_off[i + 1] - beg != 1u) return nullptr;
+  const uint32_t idx = pk_idx[beg];
+  if (idx >= comb_n || !comb_ok[idx]) return nullptr;
+  return comb + (size_t)G1_COMB_WORDS * idx;
 }
 
 BLS_HD void stage_sig(const PipeBufs& b, uint32_t i) {

@@ -71,6 +71,16 @@ struct bls_gpu_ctx {
   // device pubkey table (affine, Montgomery)
   G1A* table;
   uint32_t table_n, table_cap;
+  // fixed-base comb rows of the table's keys (curve.hpp g1_comb_mul; k_chain role 3), grown
+  // and copied with the table: room for keys [0, comb_cap), comb_cap <= table_cap
+  // ($BLS_PK_COMB_MAX_MB), of which [0, comb_n) are built, comb_ok[i] = 1 where key i has
+  // rows.  nullptr: off ($BLS_PK_COMB=0) or the allocation failed -- every set then takes
+  // the GLV chain; a load never fails because of the comb.
+  Fp* comb;
+  uint8_t* comb_ok;
+  uint32_t comb_cap, comb_n;
+  bool comb_off;
+  Fp* g1_comb;  // the generator's rows, made at creation (k_pre's RG lanes); nullptr: GLV
   uint32_t debug_flags;  // bls_gpu_set_debug_flags
   // the context's last pass failed its merged check: its next pass keeps the per-set
   // [r] sig chains rather than the Pippenger sum (plan_pass: PassShape::use_msm), so a failure
@@ -177,6 +187,8 @@ T* res_host(bls_gpu_ctx* ctx, T* dev_ptr) {
 
 extern "C" int bls_gpu_device_count(void);
 extern "C" void bls_gpu_close(bls_gpu_ctx* ctx);
+static bool pk_comb_on();  // $BLS_PK_COMB (the comb rows of the table's keys, below)
+static void g1_comb_init(bls_gpu_ctx* ctx);
 
 // ---------------------------------------------------------------------------
 // cooperative program tables: lodestar_amd/_native/coop_tables.bin next to this
@@ -530,6 +542,7 @@ int bls_gpu_init_priority(int device, int priority, bls_gpu_ctx** out) {
   ctx->mu = new std::mutex();
   ctx->device = device;
   ctx->admitted = high ? 2 : 1;
+  ctx->comb_off = !pk_comb_on();
   // every failure below releases what was made through bls_gpu_close (it tolerates
   // members that were never created) and leaves its message for bls_gpu_init_error
   auto fail = [&](const char* what, hipError_t e) {
@@ -562,6 +575,7 @@ int bls_gpu_init_priority(int device, int priority, bls_gpu_ctx** out) {
   if ((e = hipMalloc(&ctx->msm_state, sizeof(uint32_t) * MSM_STATE_WORDS)) != hipSuccess ||
       (e = hipMemset(ctx->msm_state, 0, sizeof(uint32_t) * MSM_STATE_WORDS)) != hipSuccess)
     return fail("msm_state", e);
+  if (!ctx->comb_off) g1_comb_init(ctx);
   *out = ctx;
   return 0;
 }
@@ -579,6 +593,9 @@ void bls_gpu_close(bls_gpu_ctx* ctx) {
   (void)hipSetDevice(ctx->device);
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
   if (ctx->table) (void)hipFree(ctx->table);
+  if (ctx->comb) (void)hipFree(ctx->comb);
+  if (ctx->comb_ok) (void)hipFree(ctx->comb_ok);
+  if (ctx->g1_comb) (void)hipFree(ctx->g1_comb);
   if (ctx->dev_ws) (void)hipFree(ctx->dev_ws);
   if (ctx->host_stage) (void)hipHostFree(ctx->host_stage);
   if (ctx->host_res) (void)hipHostFree(ctx->host_res);
@@ -599,6 +616,115 @@ void bls_gpu_close(bls_gpu_ctx* ctx) {
 
 const char* bls_gpu_last_error(const bls_gpu_ctx* ctx) { return ctx ? ctx->err : "no context"; }
 
+// ---------------------------------------------------------------------------
+// comb rows of the table's keys (curve.hpp g1_comb_build)
+// ---------------------------------------------------------------------------
+static bool pk_comb_on() {
+  static const bool on = [] {
+    const char* e = getenv("BLS_PK_COMB");
+    return !(e && *e && atoi(e) == 0);
+  }();
+  return on;
+}
+
+// keys whose rows one context may hold: $BLS_PK_COMB_MAX_MB of comb memory (default 4096,
+// about 2.9M keys at 1,440 B each); keys past it keep the GLV chain
+static uint32_t pk_comb_max_keys() {
+  uint64_t mb = 4096;
+  const char* e = getenv("BLS_PK_COMB_MAX_MB");
+  if (e && *e) mb = strtoull(e, nullptr, 10);
+  const uint64_t keys = (mb << 20) / (sizeof(Fp) * G1_COMB_WORDS);
+  return keys > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)keys;
+}
+
+// the comb is given up for this context (an allocation or its build failed): the rows
+// must cover a prefix of the table, so it is not tried again
+static void comb_drop(bls_gpu_ctx* ctx) {
+  (void)hipGetLastError();
+  if (ctx->comb) (void)hipFree(ctx->comb);
+  if (ctx->comb_ok) (void)hipFree(ctx->comb_ok);
+  ctx->comb = nullptr;
+  ctx->comb_ok = nullptr;
+  ctx->comb_cap = ctx->comb_n = 0;
+  ctx->comb_off = true;
+}
+
+// The generator's rows, by the builder the table's keys get (one lane); a failure only
+// leaves the per-set path's RG lanes on the GLV chain.
+static void g1_comb_init(bls_gpu_ctx* ctx) {
+  const size_t off_tmp = 256, off_ok = off_tmp + sizeof(G1J) * G1_COMB_ROWS;
+  static_assert(sizeof(G1A) <= 256, "the key sits before the builder's workspace");
+  uint8_t* buf = nullptr;
+  Fp* rows = nullptr;
+  const G1A g = g1_generator();
+  uint8_t ok = 0;
+  const bool good =
+      hipMalloc(&buf, off_ok + 16) == hipSuccess && hipMalloc(&rows, sizeof(Fp) * G1_COMB_WORDS) == hipSuccess &&
+      hipMemcpy(buf, &g, sizeof(g), hipMemcpyHostToDevice) == hipSuccess &&
+      launch_k_comb_build((const G1A*)buf, 1, (G1J*)(buf + off_tmp), rows, buf + off_ok, ctx->stream) == hipSuccess &&
+      hipStreamSynchronize(ctx->stream) == hipSuccess &&
+      hipMemcpy(&ok, buf + off_ok, 1, hipMemcpyDeviceToHost) == hipSuccess;
+  if (buf) (void)hipFree(buf);
+  if (good && ok) {
+    ctx->g1_comb = rows;
+    return;
+  }
+  (void)hipGetLastError();
+  if (rows) (void)hipFree(rows);
+}
+
+// room for the rows of a table of table_cap keys, the built rows copied as the table's are
+static void comb_grow(bls_gpu_ctx* ctx, uint32_t table_cap) {
+  if (ctx->comb_off) return;
+  const uint32_t max_keys = pk_comb_max_keys();
+  const uint32_t want = table_cap < max_keys ? table_cap : max_keys;
+  if (want <= ctx->comb_cap) return;
+  Fp* rows = nullptr;
+  uint8_t* ok = nullptr;
+  bool good = hipMalloc(&rows, sizeof(Fp) * G1_COMB_WORDS * (size_t)want) == hipSuccess &&
+              hipMalloc(&ok, (size_t)want) == hipSuccess;
+  if (good && ctx->comb_n)
+    good = hipMemcpyAsync(rows, ctx->comb, sizeof(Fp) * G1_COMB_WORDS * (size_t)ctx->comb_n, hipMemcpyDeviceToDevice,
+                          ctx->stream) == hipSuccess &&
+           hipMemcpyAsync(ok, ctx->comb_ok, ctx->comb_n, hipMemcpyDeviceToDevice, ctx->stream) == hipSuccess &&
+           hipStreamSynchronize(ctx->stream) == hipSuccess;
+  if (!good) {
+    if (rows) (void)hipFree(rows);
+    if (ok) (void)hipFree(ok);
+    comb_drop(ctx);
+    return;
+  }
+  if (ctx->comb) (void)hipFree(ctx->comb);
+  if (ctx->comb_ok) (void)hipFree(ctx->comb_ok);
+  ctx->comb = rows;
+  ctx->comb_ok = ok;
+  ctx->comb_cap = want;
+}
+
+// rows of the table's keys [comb_n, min(table_n, comb_cap)), in batches that bound the
+// builder's workspace (15 Jacobian entries per key, freed afterwards)
+static void comb_build_new(bls_gpu_ctx* ctx, uint32_t table_n) {
+  if (ctx->comb_off || !ctx->comb) return;
+  const uint32_t end = table_n < ctx->comb_cap ? table_n : ctx->comb_cap;
+  if (end <= ctx->comb_n) return;
+  const uint32_t BATCH = 1u << 16;
+  const uint32_t todo = end - ctx->comb_n;
+  G1J* tmp = nullptr;
+  bool good = hipMalloc(&tmp, sizeof(G1J) * G1_COMB_ROWS * (size_t)(todo < BATCH ? todo : BATCH)) == hipSuccess;
+  for (uint32_t at = ctx->comb_n; good && at < end; at += BATCH) {
+    const uint32_t m = end - at < BATCH ? end - at : BATCH;
+    good = launch_k_comb_build(ctx->table + at, m, tmp, ctx->comb + (size_t)G1_COMB_WORDS * at, ctx->comb_ok + at,
+                               ctx->stream) == hipSuccess;
+  }
+  good = good && hipStreamSynchronize(ctx->stream) == hipSuccess;
+  if (tmp) (void)hipFree(tmp);
+  if (!good) {
+    comb_drop(ctx);
+    return;
+  }
+  ctx->comb_n = end;
+}
+
 int64_t bls_gpu_load_pubkeys(bls_gpu_ctx* ctx, const uint8_t* pks, uint32_t n, uint32_t pk_len, int32_t* codes) {
   CTX_LOCK(ctx);
   if (pk_len != 48 && pk_len != 96) {
@@ -618,6 +744,7 @@ int64_t bls_gpu_load_pubkeys(bls_gpu_ctx* ctx, const uint8_t* pks, uint32_t n, u
     }
     ctx->table = t;
     ctx->table_cap = cap;
+    comb_grow(ctx, cap);
   }
   if (n == 0) return ctx->table_n;
   size_t in_bytes = (size_t)pk_len * n;
@@ -638,6 +765,7 @@ int64_t bls_gpu_load_pubkeys(bls_gpu_ctx* ctx, const uint8_t* pks, uint32_t n, u
   // indices (validator indices) stay aligned across contexts and calls
   for (uint32_t i = 0; i < n; ++i)
     if (host_codes[i] != 0) return ctx->table_n;
+  comb_build_new(ctx, ctx->table_n + n);
   ctx->table_n += n;
   return ctx->table_n;
 }
@@ -1228,6 +1356,12 @@ struct VerifyPass {
     b.n_chunks = sh.n_chunks;
     b.pk_table = ctx->table;
     b.pk_table_n = ctx->table_n;
+    if (ctx->comb && !(ctx->debug_flags & BLS_DEBUG_NO_PK_COMB)) {
+      b.pk_comb = ctx->comb;
+      b.pk_comb_ok = ctx->comb_ok;
+      b.pk_comb_n = ctx->comb_n;
+    }
+    if (!(ctx->debug_flags & BLS_DEBUG_NO_PK_COMB)) b.g1_comb = ctx->g1_comb;
     b.scalar_base = a.scalar_base;
     b.pack = sh.pack;
     b.mlf_pl = sh.mlf_pl;

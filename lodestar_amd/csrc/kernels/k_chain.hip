@@ -67,6 +67,13 @@ __device__ __noinline__ void g1_mul_r(G1J* out, const G1J* in, uint64_t k, G1J* 
   glv_split(k, a, b);
   *out = jac_mul_glv<Fp>(*in, a, b, T);
 }
+// [r] pk for a key of the device table that has comb rows (curve.hpp g1_comb_mul): 7
+// doublings and 16 mixed additions on the rows made at load time, no table build
+__device__ __noinline__ void g1_comb_r(G1J* out, const Fp* rows, uint64_t k) {
+  uint32_t a, b;
+  glv_split(k, a, b);
+  *out = g1_comb_mul(rows, a, b);
+}
 // out-of-line general addition for the handful of additions outside the chains
 __device__ __noinline__ void g2_add(G2J* out, const G2J* a, const G2J* b) { *out = jac_add(*a, *b); }
 
@@ -182,12 +189,22 @@ __device__ __noinline__ void chain_role_rs(Fp* chain, const G2A* sigs, const uin
   o[CH_RS + 5] = RS.z.c1;
 }
 
+// A set of exactly one table key whose rows exist takes the comb; aggregates, raw keys,
+// keys past the comb's cap and keys the builder refused take the GLV chain on pks[i].
 __device__ __noinline__ void chain_role_rp(Fp* chain, const G1J* pks, uint8_t* chain_st, const uint32_t* seed,
-                                           uint32_t scalar_base, G1J* rtab1, uint32_t i) {
+                                           uint32_t scalar_base, G1J* rtab1, const uint32_t* set_pk_off,
+                                           const uint32_t* pk_idx, const Fp* comb, const uint8_t* comb_ok,
+                                           uint32_t comb_n, uint32_t i) {
   Fp* o = chain + (size_t)CHAIN_WORDS * i;
   G1J RP;
-  const G1J pk = pks[i];
-  g1_mul_r(&RP, &pk, set_scalar(seed, scalar_base + i), rtab1 + 15ull * i);
+  const uint64_t r = set_scalar(seed, scalar_base + i);
+  const Fp* rows = set_comb_rows(set_pk_off, pk_idx, comb, comb_ok, comb_n, i);
+  if (rows) {
+    g1_comb_r(&RP, rows, r);
+  } else {
+    const G1J pk = pks[i];
+    g1_mul_r(&RP, &pk, r, rtab1 + 15ull * i);
+  }
   chain_st[4 * i + 3] = jac_is_inf(RP) ? 1 : 0;
   if (jac_is_inf(RP)) return;
   o[CH_RP + 0] = RP.x;
@@ -204,7 +221,8 @@ __device__ __noinline__ void chain_role_rp(Fp* chain, const G1J* pks, uint8_t* c
 //           once per distinct signing root
 //   role 1  psi(sig) == [x] sig                                     ~1.2k
 //   role 2  RS = [r] sig                                            ~1.9k
-//   role 3  RP = [r] pk                                             ~1.0k
+//   role 3  RP = [r] pk                                             ~0.65k GLV chain; ~0.24k on the
+//           comb rows of a table key (one key per set)
 // Results that decide the set's fate go to b.chain_st[4 i + role] (k_chain_done
 // reads them; every role that runs writes its byte, so no clearing is needed).
 // At most 256 VGPRs, so two wavefronts share a SIMD: cfg2 +1.2 % over one 394-VGPR
@@ -230,7 +248,8 @@ __global__ __launch_bounds__(BLS_BLOCK) BLS_CHAIN_ATTR void k_chain(PipeBufs b, 
   if (role == 0) chain_role_h(b.chain, b.q, b.chain_st, i);
   else if (role == 1) chain_role_sub(b.sig, b.chain_st, i);
   else if (role == 2) chain_role_rs(b.chain, b.sig, b.seed, b.scalar_base, b.rtab2, i);
-  else chain_role_rp(b.chain, b.pk, b.chain_st, b.seed, b.scalar_base, b.rtab1, i);
+  else chain_role_rp(b.chain, b.pk, b.chain_st, b.seed, b.scalar_base, b.rtab1, b.set_pk_off, b.pk_idx, b.pk_comb,
+                     b.pk_comb_ok, b.pk_comb_n, i);
 }
 
 // One lane per set after the four roles: the set's fate.

@@ -81,6 +81,25 @@ __global__ __launch_bounds__(BLS_BLOCK) void k_load_pubkeys(const uint8_t* pks, 
   codes[i] = c;
 }
 
+// Comb rows of n freshly loaded table keys (curve.hpp g1_comb_build), one lane per key:
+// rows[G1_COMB_WORDS * i ..] and ok[i] for key keys[i]; tmp holds the lane's 15 Jacobian
+// entries until they are affine (15 n G1J of workspace, not a 2 KB private frame).  Two
+// wavefronts per SIMD at the most, so its scratch reservation per queue stays under the
+// verify path's deepest kernel (lodestar_amd/build.py scratch_per_queue).
+__global__ __launch_bounds__(BLS_BLOCK) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_comb_build(
+    const G1A* keys, uint32_t n, G1J* tmp, Fp* rows, uint8_t* ok) {
+  const uint32_t i = blockIdx.x * BLS_BLOCK + threadIdx.x;
+  if (i >= n) return;
+  const G1A p = keys[i];
+  ok[i] = g1_comb_build(p, tmp + (size_t)G1_COMB_ROWS * i, rows + (size_t)G1_COMB_WORDS * i) ? 1 : 0;
+}
+
+hipError_t launch_k_comb_build(const G1A* keys, uint32_t n, G1J* tmp, Fp* rows, uint8_t* ok, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  k_comb_build<<<bls_grid_for(n), BLS_BLOCK, 0, s>>>(keys, n, tmp, rows, ok);
+  return hipGetLastError();
+}
+
 // KeyValidate (blst PublicKey.fromBytes(bytes, validate=true) [ext], as the deposit
 // path uses it, block/processDeposit.ts:56-65): decode, reject infinity, G1 subgroup.
 __global__ __launch_bounds__(BLS_BLOCK) void k_validate_pubkeys(const uint8_t* pks, uint32_t n, uint32_t pk_len,

@@ -22,6 +22,9 @@ hipError_t launch_k_pk_agg(const bls::PipeBufs& b, hipStream_t s);
 hipError_t launch_k_aggregate(const bls::PipeBufs& b, uint8_t* out96, hipStream_t s);
 hipError_t launch_k_load_pubkeys(const uint8_t* pks, uint32_t n, uint32_t pk_len, bls::G1A* out, int32_t* codes,
                                  hipStream_t s);
+// comb rows of n table keys (curve.hpp g1_comb_build): tmp = 15 n G1J of workspace
+hipError_t launch_k_comb_build(const bls::G1A* keys, uint32_t n, bls::G1J* tmp, bls::Fp* rows, uint8_t* ok,
+                               hipStream_t s);
 hipError_t launch_k_status(const bls::PipeBufs& b, hipStream_t s);
 hipError_t launch_k_validate_pubkeys(const uint8_t* pks, uint32_t n, uint32_t pk_len, int32_t* codes, hipStream_t s);
 // the front kernel of a deposit call, in k_pk's place (kernels/k_deposit.hip, bls/deposit.hpp)
