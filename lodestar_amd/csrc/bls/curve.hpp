@@ -388,10 +388,26 @@ BLS_HD Jac<F> jac_mul_glv(const Jac<F>& p, uint32_t a, uint32_t b, Jac<F>* T) {
   return acc;
 }
 
-// the scalar a + b mu mod r as 8 little-endian words (tests / the oracle side)
+// the two halves of a set's 64-bit random value: the set's group scalar is a + b mu mod r
 BLS_HD void glv_split(uint64_t r64, uint32_t& a, uint32_t& b) {
   a = (uint32_t)r64;
   b = (uint32_t)(r64 >> 32);
+}
+
+// [a + b mu]P for the halves of r64 with no table: one 32-bit double-and-add chain on P,
+// one on endo(P), one addition, all with the complete formulas -- the form of the
+// single-lane stage bodies (pipeline.hpp stage_scale / stage_exact_set), which must apply
+// the SAME group scalar as jac_mul_glv, g1_comb_mul and k_msm do: the sets of one chunk,
+// pass or sharded call are multiplied together whichever path made each f_i.  One rolled
+// loop: a single copy of the chain.
+template <class F>
+BLS_HD Jac<F> jac_mul_set_scalar(const Jac<F>& p, uint64_t r64) {
+  uint32_t k[2];
+  glv_split(r64, k[0], k[1]);
+  Jac<F> acc = jac_infinity<F>();
+#pragma unroll 1
+  for (int h = 0; h < 2; ++h) acc = jac_add(acc, jac_mul_u64(h ? jac_endo_mu(p) : p, (uint64_t)k[h]));
+  return acc;
 }
 
 // ---- fixed-base comb for [a]P + [b]sigma(P) on a G1 point that stays the same ------

@@ -7,7 +7,7 @@
 //   stage_pk          deserializeSet / getAggregatedPubkey      (worker.ts:110-116, utils.ts:5-16)
 //   stage_sig         Signature.fromBytes(sig, affine, true)    (maybeBatch.ts:23,36)
 //   stage_h2c         hash_to_G2(signingRoot)                   ([ext] blst)
-//   stage_scale       r_i * pk_i, r_i * sig_i, 64-bit r_i       ([ext] verifyMultipleSignatures)
+//   stage_scale       r_i * pk_i, r_i * sig_i, r_i = a_i + b_i mu ([ext] verifyMultipleSignatures)
 //   stage_pair_set    f_i = ML(r_i pk_i, H(m_i)) * ML(-g1, r_i sig_i)
 //   stage_req_status  per-request error precedence              (worker.ts:45, maybeBatch.ts:16-39)
 //   stage_chunk       FE(prod f_i) == 1 per chunk of >= 16 requests
@@ -166,8 +166,15 @@ BLS_HD void scalar_words_from_be32(const uint8_t* b, uint32_t k[8]) {
   }
 }
 
-// r_i = first 8 bytes of SHA-256(seed || LE32(i)), forced non-zero
-// (the reference draws randomBytesNonZero(8) per set, [ext] @chainsafe/blst).
+// The 64-bit random value of set index i: the first 8 bytes, read big-endian, of
+// SHA-256(W || LE32(i)), forced non-zero (the reference draws randomBytesNonZero(8) per
+// set, [ext] @chainsafe/blst).  W is the caller's 32-byte seed with its eight 4-byte words
+// in reverse order (bytes 28..31 first): every entry point turns the seed into words with
+// scalar_words_from_be32, and the words are hashed from index 0 up.  The value is NOT the
+// group scalar: its low and high 32 bits a, b give r_i = a + b mu mod r, mu = -x^2 (bls/
+// curve.hpp: glv_split, jac_mul_glv, g1_comb_mul, jac_mul_set_scalar; kernels/k_msm.hip),
+// and every path that multiplies a set applies that r_i.  tests/_scalarprobe.py states the
+// derivation with hashlib and integers; tests/test_scalarprobe_cpu.py pins it.
 BLS_HD uint64_t set_scalar(const uint32_t seed[8], uint32_t i) {
   uint32_t W[16];
   for (int k = 0; k < 8; ++k) W[k] = seed[k];
@@ -258,8 +265,8 @@ BLS_HD void stage_scale(const PipeBufs& b, uint32_t i) {
   if (i >= b.n_sets) return;
   uint64_t r = set_scalar(b.seed, b.scalar_base + i);
   if (b.pk_status[i] == BLS_OK && b.sig_status[i] == BLS_OK) {
-    b.rpk[i] = jac_mul_u64(b.pk[i], r);
-    b.rsig[i] = aff_mul_u64(b.sig[i], r);
+    b.rpk[i] = jac_mul_set_scalar(b.pk[i], r);
+    b.rsig[i] = b.sig[i].inf ? jac_infinity<Fp2>() : jac_mul_set_scalar(jac_from_aff(b.sig[i]), r);
   } else {
     b.rpk[i] = jac_infinity<Fp>();
     b.rsig[i] = jac_infinity<Fp2>();
@@ -392,8 +399,8 @@ BLS_HD void stage_exact_set(const PipeBufs& b, uint32_t i) {
   msg_words_from_bytes(b.msgs + 32ull * i, w);
   const G2A H = hash_to_g2(w);
   const uint64_t r = set_scalar(b.seed, b.scalar_base + i);
-  const G1J rpk = jac_mul_u64(b.pk[i], r);
-  const G2J rsig = sig.inf ? jac_infinity<Fp2>() : aff_mul_u64(sig, r);
+  const G1J rpk = jac_mul_set_scalar(b.pk[i], r);
+  const G2J rsig = sig.inf ? jac_infinity<Fp2>() : jac_mul_set_scalar(jac_from_aff(sig), r);
   b.f[i] = pair_set(rpk, H, rsig, sig.inf);
 }
 

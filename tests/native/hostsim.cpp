@@ -366,6 +366,14 @@ long long hs_load_pubkeys(const uint8_t* pks, uint32_t n, uint32_t pk_len, int32
 }
 void hs_clear_pubkeys(void) { g_table.clear(); }
 
+// The 64-bit random value of set index i under a call's 32-byte seed, the seed turned
+// into words as every entry point does it (bls_gpu.hip stage_inputs, hs_verify_batch below)
+uint64_t hs_set_scalar(const uint8_t* seed32, uint32_t i) {
+  uint32_t seed[8];
+  scalar_words_from_be32(seed32, seed);
+  return set_scalar(seed, i);
+}
+
 // Full verify pipeline on the CPU: the GPU kernels' stage bodies (pipeline.hpp) looped
 // over "lanes", planned and assembled by the same host code as bls_gpu_verify.
 int hs_verify_batch(const bls_batch* in, int32_t* verdicts, bls_stats* stats) {
