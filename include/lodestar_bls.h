@@ -388,7 +388,13 @@ int bls_gpu_fp_mul_test(bls_gpu_ctx* ctx, const uint8_t* a48, const uint8_t* b48
  * in_words words, `out` receives n records of out_words (bls_gpu_field_op_shape).
  * op: a base id (lodestar_amd/csrc/kernels/field_ops.hpp FOP_*, tests/_fieldvec.py),
  * ORed with BLS_FIELD_OP_D28 for the kernels built over the 28-bit-digit product the
- * verify path uses; without it the 32-bit column product.  -2: unknown op. */
+ * verify path uses; without it the 32-bit column product.  -2: unknown op.
+ * Ops: 0..28 the arithmetic primitives and the interpreter's linear combination, 29..31
+ * the out-of-line Fp2 products, 32 (FOP_PREDS, both flavours) the comparison predicates
+ * on one raw pair (c0, c1) -- 24 words in, one word of bits out: fp_plain_is_canonical,
+ * fp_plain_gt_half, fp_is_zero of each and fp_eq on the words as plain values (any
+ * input), then fp_lex_largest of each, fp2_lex_largest, fp2_sgn0, fp2_is_zero on them as
+ * Montgomery forms (canonical input only). */
 #define BLS_FIELD_OP_D28 0x100u
 int bls_gpu_field_op_test(bls_gpu_ctx* ctx, uint32_t op, const uint32_t* in, uint32_t n, uint32_t* out);
 int bls_gpu_field_op_shape(uint32_t op, uint32_t* in_words, uint32_t* out_words);

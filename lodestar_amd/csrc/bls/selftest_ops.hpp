@@ -1,4 +1,4 @@
-// Formula bodies of the lazy28 self-tests, shared by the CPU harness
+// Formula bodies of the lazy28 and predicate self-tests, shared by the CPU harness
 // (tests/native/hostsim.cpp hs_lz_fp_ops / hs_lz_fp2_ops) and the device field-op
 // self-test (kernels/field_ops.hpp): the same expressions run on both, on canonical
 // Montgomery operands, and return canonical Montgomery values.
@@ -42,6 +42,28 @@ BLS_HD void sf_lz_fp2_ops(const Fp2& a, const Fp2& b, Fp2 out[6]) {
   out[3] = l2_to_fp2(l2_conj(m));
   out[4] = l2_to_fp2(l2_sub(m, l2_sqr(y)));
   out[5] = l2_to_fp2(l2_mul_fp(m, y.c0));
+}
+
+// "PREDS": every comparison predicate of field.hpp on one raw pair (c0, c1), one bit each
+// (tests/_fieldvec.py PRED_BITS).  Bits 0..6 read the words as plain values and are
+// defined on any 384-bit input; bits 7..11 read them as Montgomery forms and are
+// defined on canonical input only.
+BLS_HD uint32_t sf_preds(const Fp& c0, const Fp& c1) {
+  const Fp2 a{c0, c1};
+  uint32_t r = 0;
+  r |= fp_plain_is_canonical(c0) ? 1u << 0 : 0u;
+  r |= fp_plain_is_canonical(c1) ? 1u << 1 : 0u;
+  r |= fp_plain_gt_half(c0) ? 1u << 2 : 0u;
+  r |= fp_plain_gt_half(c1) ? 1u << 3 : 0u;
+  r |= fp_is_zero(c0) ? 1u << 4 : 0u;
+  r |= fp_is_zero(c1) ? 1u << 5 : 0u;
+  r |= fp_eq(c0, c1) ? 1u << 6 : 0u;
+  r |= fp_lex_largest(c0) ? 1u << 7 : 0u;
+  r |= fp_lex_largest(c1) ? 1u << 8 : 0u;
+  r |= fp2_lex_largest(a) ? 1u << 9 : 0u;
+  r |= (fp2_sgn0(a) & 1u) << 10;
+  r |= fp2_is_zero(a) ? 1u << 11 : 0u;
+  return r;
 }
 
 }  // namespace bls

@@ -51,6 +51,7 @@ enum : uint32_t {
   FOP_FP2_MUL_W,    // fp2_mul_prim: the out-of-line lazy Fp2 product, LDS slot included
   FOP_FP2_SQR_W,    // fp2_sqr_prim
   FOP_FP2_CHAIN_W,  // four dependent products through the same slot
+  FOP_PREDS,        // sf_preds: the comparison predicates on one raw pair, one bit each (both TUs)
   FOP_COUNT
 };
 #define FOP_D28_FLAG 0x100u
@@ -80,11 +81,14 @@ constexpr int field_op_out_words(uint32_t op) {
          : op == FOP_LZ_FP2_OPS                         ? 144
          : op == FOP_SQRT                               ? 13
          : op == FOP_FP2_SQRT                           ? 25
+         : op == FOP_PREDS                              ? 1
                                                         : 12;
 }
 
 // ops only the 28-bit-digit translation unit has
-constexpr bool field_op_d28_only(uint32_t op) { return op == FOP_CANON3 || op >= FOP_SQR_D28_LAZY; }
+constexpr bool field_op_d28_only(uint32_t op) {
+  return op == FOP_CANON3 || (op >= FOP_SQR_D28_LAZY && op != FOP_PREDS);
+}
 
 #if defined(BLS_FP_D28)
 #define FOP_IS_D28 true
@@ -123,6 +127,7 @@ __device__ __forceinline__ void field_op_body(const uint32_t* x, uint32_t* y) {
   else if constexpr (OP == FOP_MUL) fop_st(y, 0, fp_mul(fop_ld(x, 0), fop_ld(x, 1)));
   else if constexpr (OP == FOP_SQR) fop_st(y, 0, fp_sqr(fop_ld(x, 0)));
   else if constexpr (OP == FOP_MUL_LAZY) fop_st(y, 0, fp_mul_lazy(fop_ld(x, 0), fop_ld(x, 1)));
+  else if constexpr (OP == FOP_PREDS) y[0] = sf_preds(fop_ld(x, 0), fop_ld(x, 1));
 #if defined(BLS_FP_D28)
   else if constexpr (OP == FOP_SQR_D28_LAZY) fop_st(y, 0, fp_sqr_d28_lazy(fop_ld(x, 0)));
   else if constexpr (OP == FOP_FP2_MUL_D28)
@@ -258,6 +263,7 @@ static hipError_t field_op_launch(uint32_t op, const uint32_t* in, uint32_t n, u
     FOP_CASE(FOP_MUL);
     FOP_CASE(FOP_SQR);
     FOP_CASE(FOP_MUL_LAZY);
+    FOP_CASE(FOP_PREDS);
 #if defined(BLS_FP_D28)
     FOP_CASE(FOP_CANON3);
     FOP_CASE(FOP_SQR_D28_LAZY);

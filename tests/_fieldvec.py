@@ -30,6 +30,7 @@ N_RANDOM = 300
 (ADD, SUB, NEG, DBL, HALF, ADD_NR, SUB_NR, REDUCE_ONCE, REDUCE_2P, CANON3, MUL, SQR, MUL_LAZY, SQR_D28_LAZY,
  FP2_MUL_D28, FP2_SQR_D28, FP2_MUL, FP2_SQR, FP2_MUL_S, LZ_MUL_RAW, LZ_SQR_RAW, LZ_FP_OPS, LZ_FP2_OPS, INV, INV_GCD,
  SQRT, FP2_INV, FP2_SQRT, LIN8) = range(29)
+PREDS = 32  # after the three fp2_*_prim ops of tests/test_gpu_fp2_prim.py (29..31)
 
 
 def limbs(v: int, n: int = 12) -> list[int]:
@@ -440,6 +441,64 @@ def _check_lin8(rec, out):
         return f"{what} = {got:#x}, want {lin8_total(rec) % P:#x} (mod p)"
 
 
+# ---- PREDS: the comparison predicates (bls/selftest_ops.hpp sf_preds) -----------------------
+# One output word, one bit per predicate.  Bits 0..6 read the two input values as plain
+# 384-bit integers and are defined (and checked) on ANY input.  Bits 7..11 read them as
+# Montgomery forms c R mod p; they are defined on canonical input only, so a bit is
+# checked only when every value it reads is below p.
+PRED_BITS = ("fp_plain_is_canonical(c0)", "fp_plain_is_canonical(c1)", "fp_plain_gt_half(c0)", "fp_plain_gt_half(c1)",
+             "fp_is_zero(c0)", "fp_is_zero(c1)", "fp_eq(c0, c1)", "fp_lex_largest(c0)", "fp_lex_largest(c1)",
+             "fp2_lex_largest", "fp2_sgn0", "fp2_is_zero")
+PRED_PLAIN_MASK = 0x7F
+
+
+def preds_ref(c0: int, c1: int) -> tuple[int, int]:
+    """(expected word, mask of the bits defined on this input) for raw values c0, c1"""
+    h = (P - 1) // 2
+    bits = [c0 < P, c1 < P, c0 > h, c1 > h, c0 == 0, c1 == 0, c0 == c1]
+    mask = PRED_PLAIN_MASK
+    p0, p1 = unmont(c0 % P), unmont(c1 % P)
+    bits += [p0 > h, p1 > h, (p1 > h) if p1 != 0 else (p0 > h), (p0 & 1) | (int(p0 == 0) & (p1 & 1)),
+             p0 == 0 and p1 == 0]
+    if c0 < P:
+        mask |= 1 << 7
+    if c1 < P:
+        mask |= 1 << 8
+    if c0 < P and c1 < P:
+        mask |= 7 << 9
+    return sum(int(b) << k for k, b in enumerate(bits)), mask
+
+
+def preds_records(rng) -> list:
+    h = (P - 1) // 2
+    plain = [0, 1, h, h + 1, P - 2, P - 1, P, P + 1, 2 * P - 1, 2 ** 381 - 1, 2 ** 384 - 1]
+    for k in range(12):
+        plain += [P + (1 << (32 * k)), P - (1 << (32 * k)), h + (1 << (32 * k)), h - (1 << (32 * k))]
+    assert all(0 <= v < R for v in plain)
+    recs = [(v, plain[(7 * k + 3) % len(plain)]) for k, v in enumerate(plain)]
+    recs += [(plain[(5 * k + 1) % len(plain)], v) for k, v in enumerate(plain)]
+    recs += [(v, v) for v in plain[:11]]  # fp_eq; and values that differ in one limb only
+    recs += [(h, h ^ (1 << (32 * k))) for k in range(12)]
+    # Montgomery forms of the values at which the sign predicates change, every pair of
+    # them: c1 == 0 (the c0 fallback of fp2_lex_largest) and c0 == 0 (the z0 & s1 term of
+    # fp2_sgn0) included
+    edge = [mont(v) for v in (0, 1, 2, h, h + 1, P - 1)]
+    recs += [(a, b) for a in edge for b in edge]
+    recs += [(rng.randrange(P), 0) for _ in range(8)] + [(0, rng.randrange(P)) for _ in range(8)]
+    for k in range(N_RANDOM):
+        bound = P if k % 2 == 0 else R
+        recs.append((rng.randrange(bound), rng.randrange(bound)))
+    return recs
+
+
+def _check_preds(rec, out):
+    want, mask = preds_ref(*rec)
+    diff = (out[0] ^ want) & mask
+    if diff or out[0] >> len(PRED_BITS):
+        bad = [f"{PRED_BITS[k]} = {out[0] >> k & 1}, want {want >> k & 1}" for k in range(len(PRED_BITS)) if diff >> k & 1]
+        return f"predicates on{hx(rec)}: {'; '.join(bad) or 'bits set past the table'} (word {out[0]:#x})"
+
+
 # ---- the sets -------------------------------------------------------------------------------
 def build_sets() -> list[VectorSet]:
     rng = random.Random(0xF1E1D)
@@ -504,6 +563,7 @@ def build_sets() -> list[VectorSet]:
         S("fp2_inv", FP2_INV, True, fp2_inv_vals, pack_mont, _check_fp2_inv),
         S("fp2_sqrt", FP2_SQRT, True, fp2_sqrt_inputs(rng), pack_mont, _check_fp2_sqrt),
         S("coop_lin", LIN8, True, lin8_records(rng), _pack_lin8, _check_lin8),
+        S("preds", PREDS, False, preds_records(rng), _pack_fp, _check_preds),
     ]
 
 
@@ -521,7 +581,7 @@ def sets() -> dict:
 SET_NAMES = ("fp_add", "fp_sub", "fp_neg", "fp_dbl", "fp_half", "fp_add_nr", "fp_sub_nr", "fp_reduce_once",
              "fp_reduce_2p", "fp_canon3", "fp_mul", "fp_sqr", "fp_mul_lazy", "fp_sqr_d28_lazy", "fp2_mul_d28",
              "fp2_sqr_d28", "fp2_mul", "fp2_sqr", "fp2_mul_s", "lz_mul_w", "lz_sqr_w", "lz_fp_ops", "lz_fp2_ops",
-             "fp_inv", "fp_inv_gcd", "fp_sqrt", "fp2_inv", "fp2_sqrt", "coop_lin")
+             "fp_inv", "fp_inv_gcd", "fp_sqrt", "fp2_inv", "fp2_sqrt", "coop_lin", "preds")
 D28_ONLY = frozenset(("fp_canon3", "fp_sqr_d28_lazy", "fp2_mul_d28", "fp2_sqr_d28", "fp2_mul", "fp2_sqr", "fp2_mul_s",
                       "lz_mul_w", "lz_sqr_w", "lz_fp_ops", "lz_fp2_ops", "fp_inv", "fp_inv_gcd", "fp_sqrt", "fp2_inv",
                       "fp2_sqrt", "coop_lin"))

@@ -188,6 +188,14 @@ int hs_fp2_sqrt(const uint8_t* a, uint8_t* out) {
   return ok;
 }
 int hs_fp2_sgn0(const uint8_t* a) { return (int)fp2_sgn0(rd_fp2(a)); }
+// the device self-test's predicate word (bls/selftest_ops.hpp sf_preds) on a raw pair of
+// little-endian limbs, no conversion
+uint32_t hs_preds_raw(const uint8_t* c0c1) {
+  Fp c0, c1;
+  memcpy(c0.l, c0c1, 48);
+  memcpy(c1.l, c0c1 + 48, 48);
+  return sf_preds(c0, c1);
+}
 
 void hs_fp12_mul(const uint8_t* a, const uint8_t* b, uint8_t* out) { wr_fp12(fp12_mul(rd_fp12(a), rd_fp12(b)), out); }
 void hs_fp12_sqr(const uint8_t* a, uint8_t* out) { wr_fp12(fp12_sqr(rd_fp12(a)), out); }
@@ -289,6 +297,12 @@ int hs_g2_in_subgroup(const uint8_t* g2) { return g2_in_subgroup(rd_g2(g2)); }
 int hs_g1_decompress(const uint8_t* pk48, uint8_t* out96) {
   G1A a;
   int32_t code = g1_decompress48(pk48, a);
+  if (code == BLS_OK) g1_serialize96(a, out96);
+  return code;
+}
+int hs_g1_deserialize(const uint8_t* pk96, uint8_t* out96) {
+  G1A a;
+  int32_t code = g1_deserialize96(pk96, a);
   if (code == BLS_OK) g1_serialize96(a, out96);
   return code;
 }

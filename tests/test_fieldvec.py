@@ -38,7 +38,7 @@ def test_records_match_the_library_shapes():
                 assert len(w) == iw.value and all(0 <= x < 1 << 32 for x in w), s.name
         if s.d28_only:
             assert lib.bls_gpu_field_op_shape(s.op, ctypes.byref(iw), ctypes.byref(ow)) == -2, s.name
-    assert lib.bls_gpu_field_op_shape(len(SETS), ctypes.byref(iw), ctypes.byref(ow)) == -2
+    assert lib.bls_gpu_field_op_shape(V.PREDS + 1, ctypes.byref(iw), ctypes.byref(ow)) == -2
     assert lib.bls_gpu_field_op_shape(0x200, ctypes.byref(iw), ctypes.byref(ow)) == -2
 
 
@@ -121,12 +121,14 @@ def _run_host(hostsim, name, rec):
     if name == "fp2_sqrt":
         ok = hostsim.hs_fp2_sqrt(f2b(rec), o)
         return [int(ok)] + V.limbs(V.mont(fp(o.raw[:48]))) + V.limbs(V.mont(fp(o.raw[48:96])))
+    if name == "preds":
+        return [hostsim.hs_preds_raw(_le(rec[0]) + _le(rec[1])) & 0xFFFFFFFF]
     raise KeyError(name)
 
 
 HOST_SETS = ("fp_add", "fp_sub", "fp_half", "fp_mul", "fp_sqr", "fp_mul_lazy", "fp_sqr_d28_lazy", "fp2_mul_d28",
              "fp2_sqr_d28", "fp2_mul_s", "lz_mul_w", "lz_sqr_w", "lz_fp_ops", "lz_fp2_ops", "fp_inv_gcd", "fp_sqrt",
-             "fp2_sqrt")
+             "fp2_sqrt", "preds")
 
 
 @pytest.mark.parametrize("name", HOST_SETS)

@@ -49,7 +49,7 @@ def test_field_op(gpu, name, flavour):
 def test_field_op_unknown_is_refused(gpu):
     from lodestar_amd.native import NativeError
 
-    for op in (len(V.SET_NAMES), V.CANON3, V.LIN8, 0x200):  # past the table; d28-only ops without the flag
+    for op in (V.PREDS + 1, V.CANON3, V.LIN8, 0x200):  # past the table; d28-only ops without the flag
         with pytest.raises(NativeError):
             gpu.field_op_shape(op)
 

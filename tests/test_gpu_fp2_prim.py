@@ -21,8 +21,8 @@ pytestmark = pytest.mark.gpu
 R = 1 << 384
 R_INV = pow(R, -1, P)
 BOUND = 2 * P  # exclusive, every coefficient
-# base op ids (csrc/kernels/field_ops.hpp), appended after the sets of tests/_fieldvec.py
-FP2_MUL_W = len(V.SET_NAMES)
+# base op ids (csrc/kernels/field_ops.hpp), right after coop_lin's
+FP2_MUL_W = V.LIN8 + 1
 FP2_SQR_W = FP2_MUL_W + 1
 FP2_CHAIN_W = FP2_MUL_W + 2
 EDGES = [0, R % P, P - 1, BOUND - 1]  # 0, Montgomery 1, p - 1, the bound - 1
