@@ -166,9 +166,39 @@ const char* bls_gpu_last_error(const bls_gpu_ctx* ctx);
  * aligned across contexts).  Returns the new table size (>= 0) or < 0 on failure.
  * Beside the 100 B table entry the load builds 1,440 B of comb rows per key (15 affine
  * multiples; [r] pk of a single-key set runs on them), up to $BLS_PK_COMB_MAX_MB MiB per
- * context (default 4096; keys past it, or every key if that memory cannot be had, verify
- * through the per-set chain as before; $BLS_PK_COMB=0: no rows). */
+ * table (default 4096; keys past it, or every key if that memory cannot be had, verify
+ * through the per-set chain as before; $BLS_PK_COMB=0: no rows).
+ * A context created by bls_gpu_init owns a private table.  When contexts share one
+ * (bls_gpu_share_pubkeys) a load through any of them appends for all of them, the return
+ * value is the shared size, and all-or-nothing holds for every sharer at once.  Loads of
+ * one table run one at a time; calls in flight on the other contexts are not blocked and
+ * see the table as it was when they began -- the new keys (and a table that had to grow)
+ * are published only after they are complete on the device. */
 int64_t bls_gpu_load_pubkeys(bls_gpu_ctx* ctx, const uint8_t* pks, uint32_t n, uint32_t pk_len, int32_t* codes);
+
+/* Make ctx use the key table of `with` (same device): one table per device instead of one
+ * replica per context (the reference has one Index2PubkeyCache per process).  ctx must
+ * hold no keys; it may already share an (empty) table with other contexts, which keep it.
+ * Afterwards the two are peers: a load through either appends for both, every verify call
+ * of either reads the same device memory, and the table lives until the last context
+ * using it is closed, in any order of closes.  $BLS_PK_COMB_MAX_MB then caps the rows per
+ * table, not per context; BLS_DEBUG_NO_PK_COMB stays a per-context flag.  Returns 0 on
+ * success and when the two already share; -2 for a NULL argument, ctx == with, contexts
+ * on different devices, or a ctx whose table is not empty (message in
+ * bls_gpu_last_error(ctx)).  The function takes both contexts' locks, so it waits for a
+ * call in flight on either. */
+int bls_gpu_share_pubkeys(bls_gpu_ctx* ctx, bls_gpu_ctx* with);
+
+/* The key table ctx uses. */
+typedef struct bls_pubkeys_info {
+  uint64_t table_id;      /* equal for contexts sharing a table; unique per table in the process; never 0 */
+  uint32_t n_keys;        /* keys loaded (the next key's index) */
+  uint32_t capacity;      /* keys the current buffers have room for */
+  uint32_t comb_keys;     /* keys [0, comb_keys) were offered comb rows */
+  uint32_t n_contexts;    /* open contexts using the table */
+  uint64_t device_bytes;  /* table + rows + comb_ok of the current generation, counted once */
+} bls_pubkeys_info;
+int bls_gpu_pubkeys_info(bls_gpu_ctx* ctx, bls_pubkeys_info* out);
 
 /* KeyValidate for n public keys (blst PublicKey.fromBytes(bytes, validate=true) [ext],
  * the check deposits get before a key enters the registry, state-transition

@@ -340,6 +340,21 @@ class GpuBlsVerifier {
       }
       this.slotCtxs.push(mine);
     }
+    // one key table per distinct device id (opts.sharePubkeys, default on): the first context
+    // opened on a device -- the main-thread lane on the first -- owns it, every other context
+    // there shares it (bls_gpu_share_pubkeys).  tableCtxs: the contexts a load goes through,
+    // one per device in `devices` order; null with the option off or an addon without
+    // sharePubkeys (an older build, a stand-in): every context then keeps its own replica.
+    this.tableCtxs = null;
+    if (opts.sharePubkeys !== false && typeof addon.sharePubkeys === "function") {
+      const owner = new Map();
+      for (const c of [this.mainCtx].concat(this.ctxs)) {
+        const dev = devices[c.slot];
+        if (owner.has(dev)) addon.sharePubkeys(c.handle, owner.get(dev).handle);
+        else owner.set(dev, c);
+      }
+      this.tableCtxs = Array.from(owner.values());
+    }
     const uvSize = opts.uvThreadpoolSize || UV_POOL_AT_LOAD;
     const warn = opts.warn || ((m) => console.warn(m));
     if (this.ctxs.length + 2 > uvSize && (opts.warn || !warnedPoolSize)) {
@@ -377,11 +392,12 @@ class GpuBlsVerifier {
     return this.jobs.length - this.jobsHead;
   }
 
-  /** Append validator pubkeys (48 B compressed each) to every context's device table on
-   * every device.  All or nothing (bls_gpu_load_pubkeys appends no key of a batch holding
-   * a bad one), so indices stay aligned across contexts and devices. */
+  /** Append validator pubkeys (48 B compressed each) to the device table of every device:
+   * once per device where its contexts share one table (sharePubkeys), else context by
+   * context.  All or nothing (bls_gpu_load_pubkeys appends no key of a batch holding a bad
+   * one), first device first, so indices stay aligned across contexts and devices. */
   loadPubkeys(pks48) {
-    [this.mainCtx].concat(this.ctxs).forEach((c, i) => {
+    (this.tableCtxs || [this.mainCtx].concat(this.ctxs)).forEach((c, i) => {
       const codes = this.addon.loadPubkeys(c.handle, pks48, 48);
       const bad = codes.findIndex((x) => x !== 0);
       if (bad >= 0) throw Error(i === 0 ? `invalid pubkey at batch index ${bad}; no key appended` : "pubkey tables diverged");

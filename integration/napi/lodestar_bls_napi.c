@@ -203,6 +203,54 @@ static napi_value js_load_pubkeys(napi_env env, napi_callback_info info) {
   return out;
 }
 
+/* sharePubkeys(handle, withHandle): handle uses withHandle's key table from here on
+ * (bls_gpu_share_pubkeys; synchronous -- it only waits for calls in flight on the two) */
+static napi_value js_share_pubkeys(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  bls_handle* h = argc > 0 ? get_handle(env, argv[0]) : NULL;
+  bls_handle* with = argc > 1 ? get_handle(env, argv[1]) : NULL;
+  if (!h || !with) {
+    napi_throw_type_error(env, NULL, "sharePubkeys(handle, withHandle)");
+    return NULL;
+  }
+  if (bls_gpu_share_pubkeys(h->ctx, with->ctx) != 0) {
+    napi_throw_error(env, NULL, bls_gpu_last_error(h->ctx));
+    return NULL;
+  }
+  return NULL;
+}
+
+/* pubkeysInfo(handle) -> {tableId, nKeys, capacity, combKeys, nContexts, deviceBytes}
+ * (bls_pubkeys_info; tableId and deviceBytes as numbers: both stay far below 2^53) */
+static napi_value js_pubkeys_info(napi_env env, napi_callback_info info) {
+  size_t argc = 1;
+  napi_value argv[1];
+  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  bls_handle* h = argc > 0 ? get_handle(env, argv[0]) : NULL;
+  if (!h) {
+    napi_throw_type_error(env, NULL, "pubkeysInfo(handle)");
+    return NULL;
+  }
+  bls_pubkeys_info pi;
+  if (bls_gpu_pubkeys_info(h->ctx, &pi) != 0) {
+    napi_throw_error(env, NULL, bls_gpu_last_error(h->ctx));
+    return NULL;
+  }
+  const char* names[6] = {"tableId", "nKeys", "capacity", "combKeys", "nContexts", "deviceBytes"};
+  const double vals[6] = {(double)pi.table_id,  (double)pi.n_keys,     (double)pi.capacity,
+                          (double)pi.comb_keys, (double)pi.n_contexts, (double)pi.device_bytes};
+  napi_value obj;
+  CHECK(env, napi_create_object(env, &obj));
+  for (int i = 0; i < 6; ++i) {
+    napi_value v;
+    CHECK(env, napi_create_double(env, vals[i], &v));
+    CHECK(env, napi_set_named_property(env, obj, names[i], v));
+  }
+  return obj;
+}
+
 enum { JOB_VERIFY = 0, JOB_PARTIAL = 1, JOB_FINAL = 2, JOB_SAME_MSG = 3, JOB_DEPOSITS = 4 };
 
 typedef struct {
@@ -639,6 +687,8 @@ static napi_value module_init(napi_env env, napi_value exports) {
       {"init", NULL, js_init, NULL, NULL, NULL, napi_default, NULL},
       {"close", NULL, js_close, NULL, NULL, NULL, napi_default, NULL},
       {"loadPubkeys", NULL, js_load_pubkeys, NULL, NULL, NULL, napi_default, NULL},
+      {"sharePubkeys", NULL, js_share_pubkeys, NULL, NULL, NULL, napi_default, NULL},
+      {"pubkeysInfo", NULL, js_pubkeys_info, NULL, NULL, NULL, napi_default, NULL},
       {"verify", NULL, js_verify, NULL, NULL, NULL, napi_default, NULL},
       {"verifySync", NULL, js_verify_sync, NULL, NULL, NULL, napi_default, NULL},
       {"sszRoots", NULL, js_ssz_roots, NULL, NULL, NULL, napi_default, NULL},

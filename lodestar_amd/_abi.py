@@ -46,6 +46,8 @@ SYMBOLS = (
     "bls_gpu_close",
     "bls_gpu_last_error",
     "bls_gpu_load_pubkeys",
+    "bls_gpu_share_pubkeys",
+    "bls_gpu_pubkeys_info",
     "bls_gpu_verify",
     "bls_gpu_verify_many",
     "bls_gpu_verify_same_message",
@@ -173,6 +175,19 @@ class BlsAdmission(ctypes.Structure):
     ]
 
 
+class BlsPubkeysInfo(ctypes.Structure):
+    """bls_pubkeys_info: the key table a context uses (its own, or one it shares)"""
+
+    _fields_ = [
+        ("table_id", ctypes.c_uint64),
+        ("n_keys", ctypes.c_uint32),
+        ("capacity", ctypes.c_uint32),
+        ("comb_keys", ctypes.c_uint32),
+        ("n_contexts", ctypes.c_uint32),
+        ("device_bytes", ctypes.c_uint64),
+    ]
+
+
 class BlsStats(ctypes.Structure):
     _fields_ = [
         ("batch_retries", ctypes.c_uint32),
@@ -204,6 +219,10 @@ def bind(lib: ctypes.CDLL) -> ctypes.CDLL:
         lib.bls_gpu_last_error.restype = ctypes.c_char_p
         lib.bls_gpu_load_pubkeys.argtypes = [vp, vp, u32, u32, vp]
         lib.bls_gpu_load_pubkeys.restype = ctypes.c_int64
+        lib.bls_gpu_share_pubkeys.argtypes = [vp, vp]
+        lib.bls_gpu_share_pubkeys.restype = i32
+        lib.bls_gpu_pubkeys_info.argtypes = [vp, ctypes.POINTER(BlsPubkeysInfo)]
+        lib.bls_gpu_pubkeys_info.restype = i32
         lib.bls_gpu_verify.argtypes = [vp, ctypes.POINTER(BlsBatch), vp, ctypes.POINTER(BlsStats)]
         lib.bls_gpu_verify.restype = i32
         lib.bls_gpu_verify_many.argtypes = [vp, ctypes.POINTER(BlsBatch), u32, vp, ctypes.POINTER(BlsStats)]

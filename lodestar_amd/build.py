@@ -312,6 +312,13 @@ def build_comb_host(verbose: bool = True, out: Path | None = None, extra: list[s
     return _build_host_program("comb_host", (), verbose, out, extra)
 
 
+def build_pk_table_host(verbose: bool = True, out: Path | None = None, extra: list[str] | None = None) -> Path:
+    """The shared key table's bookkeeping (bls/pk_table.hpp) under reader and loader threads
+    over a poisoning host allocator (tests/native/pk_table_host.cpp), a stand-alone program
+    for tests/; `extra` as above."""
+    return _build_host_program("pk_table_host", (), verbose, out, ["-pthread"] + (extra or []))
+
+
 def build_cpu_baseline(verbose: bool = True) -> Path:
     """The C++ CPU baseline under oracle/cpu (benchmark / test infrastructure, "not
     blst"; oracle/cpu/bls_cpu.cpp), next to its source: bench.py's cpu_baseline leg
@@ -356,4 +363,5 @@ if __name__ == "__main__":
     build_plan_host()
     build_deposit_host()
     build_comb_host()
+    build_pk_table_host()
     build_cpu_baseline()

@@ -53,6 +53,7 @@
 
 #include "bls/deposit.hpp"
 #include "bls/group_decode.hpp"
+#include "bls/pk_table.hpp"
 #include "bls/plan.hpp"
 #include "launchers.hpp"
 
@@ -68,19 +69,17 @@ struct bls_gpu_ctx {
   hipEvent_t ev_wait;
   bool wait_block;
   char err[512];
-  // device pubkey table (affine, Montgomery)
-  G1A* table;
-  uint32_t table_n, table_cap;
-  // fixed-base comb rows of the table's keys (curve.hpp g1_comb_mul; k_chain role 3), grown
-  // and copied with the table: room for keys [0, comb_cap), comb_cap <= table_cap
-  // ($BLS_PK_COMB_MAX_MB), of which [0, comb_n) are built, comb_ok[i] = 1 where key i has
-  // rows.  nullptr: off ($BLS_PK_COMB=0) or the allocation failed -- every set then takes
-  // the GLV chain; a load never fails because of the comb.
-  Fp* comb;
-  uint8_t* comb_ok;
-  uint32_t comb_cap, comb_n;
-  bool comb_off;
-  Fp* g1_comb;  // the generator's rows, made at creation (k_pre's RG lanes); nullptr: GLV
+  // The device pubkey table (affine, Montgomery), private until bls_gpu_share_pubkeys joins
+  // another context's: bls/pk_table.hpp.  A generation holds the table, the fixed-base
+  // comb rows of its keys (curve.hpp g1_comb_mul; k_chain role 3), grown and copied with
+  // the table -- room for keys [0, comb_cap), comb_cap <= cap ($BLS_PK_COMB_MAX_MB), of
+  // which [0, comb_n) are built -- and comb_ok[i] = 1 where key i has rows.  No rows: off
+  // ($BLS_PK_COMB=0) or an allocation failed -- every set then takes the GLV chain; a load
+  // never fails because of the comb.  The table also owns the generator's rows, made at
+  // its creation (k_pre's RG lanes); nullptr: GLV.  Held through a heap pointer as mu is
+  // (the struct is zeroed at creation).  An entry point that hands table pointers to a
+  // kernel takes one snapshot and uses only that (pk_snapshot).
+  std::shared_ptr<PkTable>* pkt;
   uint32_t debug_flags;  // bls_gpu_set_debug_flags
   // the context's last pass failed its merged check: its next pass keeps the per-set
   // [r] sig chains rather than the Pippenger sum (plan_pass: PassShape::use_msm), so a failure
@@ -188,7 +187,8 @@ T* res_host(bls_gpu_ctx* ctx, T* dev_ptr) {
 extern "C" int bls_gpu_device_count(void);
 extern "C" void bls_gpu_close(bls_gpu_ctx* ctx);
 static bool pk_comb_on();  // $BLS_PK_COMB (the comb rows of the table's keys, below)
-static void g1_comb_init(bls_gpu_ctx* ctx);
+static void pk_table_new(bls_gpu_ctx* ctx);
+static void pk_table_release(bls_gpu_ctx* ctx);
 
 // ---------------------------------------------------------------------------
 // cooperative program tables: lodestar_amd/_native/coop_tables.bin next to this
@@ -542,7 +542,6 @@ int bls_gpu_init_priority(int device, int priority, bls_gpu_ctx** out) {
   ctx->mu = new std::mutex();
   ctx->device = device;
   ctx->admitted = high ? 2 : 1;
-  ctx->comb_off = !pk_comb_on();
   // every failure below releases what was made through bls_gpu_close (it tolerates
   // members that were never created) and leaves its message for bls_gpu_init_error
   auto fail = [&](const char* what, hipError_t e) {
@@ -575,7 +574,7 @@ int bls_gpu_init_priority(int device, int priority, bls_gpu_ctx** out) {
   if ((e = hipMalloc(&ctx->msm_state, sizeof(uint32_t) * MSM_STATE_WORDS)) != hipSuccess ||
       (e = hipMemset(ctx->msm_state, 0, sizeof(uint32_t) * MSM_STATE_WORDS)) != hipSuccess)
     return fail("msm_state", e);
-  if (!ctx->comb_off) g1_comb_init(ctx);
+  pk_table_new(ctx);
   *out = ctx;
   return 0;
 }
@@ -592,10 +591,7 @@ void bls_gpu_close(bls_gpu_ctx* ctx) {
   }
   (void)hipSetDevice(ctx->device);
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-  if (ctx->table) (void)hipFree(ctx->table);
-  if (ctx->comb) (void)hipFree(ctx->comb);
-  if (ctx->comb_ok) (void)hipFree(ctx->comb_ok);
-  if (ctx->g1_comb) (void)hipFree(ctx->g1_comb);
+  pk_table_release(ctx);  // the table goes with its last context
   if (ctx->dev_ws) (void)hipFree(ctx->dev_ws);
   if (ctx->host_stage) (void)hipHostFree(ctx->host_stage);
   if (ctx->host_res) (void)hipHostFree(ctx->host_res);
@@ -627,7 +623,7 @@ static bool pk_comb_on() {
   return on;
 }
 
-// keys whose rows one context may hold: $BLS_PK_COMB_MAX_MB of comb memory (default 4096,
+// keys whose rows one table may hold: $BLS_PK_COMB_MAX_MB of comb memory (default 4096,
 // about 2.9M keys at 1,440 B each); keys past it keep the GLV chain
 static uint32_t pk_comb_max_keys() {
   uint64_t mb = 4096;
@@ -637,21 +633,51 @@ static uint32_t pk_comb_max_keys() {
   return keys > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)keys;
 }
 
-// the comb is given up for this context (an allocation or its build failed): the rows
-// must cover a prefix of the table, so it is not tried again
-static void comb_drop(bls_gpu_ctx* ctx) {
+// device memory as bls/pk_table.hpp sees it
+static void* pk_mem_alloc(size_t bytes) {
+  void* p = nullptr;
+  if (hipMalloc(&p, bytes) == hipSuccess) return p;
   (void)hipGetLastError();
-  if (ctx->comb) (void)hipFree(ctx->comb);
-  if (ctx->comb_ok) (void)hipFree(ctx->comb_ok);
-  ctx->comb = nullptr;
-  ctx->comb_ok = nullptr;
-  ctx->comb_cap = ctx->comb_n = 0;
-  ctx->comb_off = true;
+  return nullptr;
 }
+static void pk_mem_free(void* p) { (void)hipFree(p); }
+static bool pk_mem_copy(void* dst, const void* src, size_t bytes, void* stream) {
+  return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream) == hipSuccess;
+}
+static bool pk_mem_sync(void* stream) { return hipStreamSynchronize((hipStream_t)stream) == hipSuccess; }
+static const PkMem g_pk_mem = {pk_mem_alloc, pk_mem_free, pk_mem_copy, pk_mem_sync};
+
+static Fp* g1_comb_make(bls_gpu_ctx* ctx);
+
+// a context's own table, empty (at creation); $BLS_PK_COMB decides whether it grows rows
+static void pk_table_new(bls_gpu_ctx* ctx) {
+  const bool comb_off = !pk_comb_on();
+  auto t = std::make_shared<PkTable>(&g_pk_mem, ctx->device, sizeof(G1A), sizeof(Fp) * G1_COMB_WORDS, comb_off);
+  if (!comb_off) t->set_g1_comb(g1_comb_make(ctx));
+  t->attach();
+  ctx->pkt = new std::shared_ptr<PkTable>(std::move(t));
+}
+
+// the context lets go of its table: the last one out frees it (no table mutex is held)
+static void pk_table_release(bls_gpu_ctx* ctx) {
+  if (!ctx->pkt) return;
+  (*ctx->pkt)->detach();
+  delete ctx->pkt;
+  ctx->pkt = nullptr;
+}
+
+// The table as one call sees it from its first kernel to its last stream synchronisation.
+struct PkView {
+  PkSnapshot snap;
+  const G1A* table() const { return (const G1A*)snap.gen->table_p(); }
+  const Fp* comb() const { return (const Fp*)snap.gen->comb_p(); }
+  const uint8_t* comb_ok() const { return snap.gen->comb_ok_p(); }
+};
+static PkView pk_snapshot(const bls_gpu_ctx* ctx) { return PkView{(*ctx->pkt)->snapshot()}; }
 
 // The generator's rows, by the builder the table's keys get (one lane); a failure only
 // leaves the per-set path's RG lanes on the GLV chain.
-static void g1_comb_init(bls_gpu_ctx* ctx) {
+static Fp* g1_comb_make(bls_gpu_ctx* ctx) {
   const size_t off_tmp = 256, off_ok = off_tmp + sizeof(G1J) * G1_COMB_ROWS;
   static_assert(sizeof(G1A) <= 256, "the key sits before the builder's workspace");
   uint8_t* buf = nullptr;
@@ -665,66 +691,36 @@ static void g1_comb_init(bls_gpu_ctx* ctx) {
       hipStreamSynchronize(ctx->stream) == hipSuccess &&
       hipMemcpy(&ok, buf + off_ok, 1, hipMemcpyDeviceToHost) == hipSuccess;
   if (buf) (void)hipFree(buf);
-  if (good && ok) {
-    ctx->g1_comb = rows;
-    return;
-  }
+  if (good && ok) return rows;
   (void)hipGetLastError();
   if (rows) (void)hipFree(rows);
+  return nullptr;
 }
 
-// room for the rows of a table of table_cap keys, the built rows copied as the table's are
-static void comb_grow(bls_gpu_ctx* ctx, uint32_t table_cap) {
-  if (ctx->comb_off) return;
-  const uint32_t max_keys = pk_comb_max_keys();
-  const uint32_t want = table_cap < max_keys ? table_cap : max_keys;
-  if (want <= ctx->comb_cap) return;
-  Fp* rows = nullptr;
-  uint8_t* ok = nullptr;
-  bool good = hipMalloc(&rows, sizeof(Fp) * G1_COMB_WORDS * (size_t)want) == hipSuccess &&
-              hipMalloc(&ok, (size_t)want) == hipSuccess;
-  if (good && ctx->comb_n)
-    good = hipMemcpyAsync(rows, ctx->comb, sizeof(Fp) * G1_COMB_WORDS * (size_t)ctx->comb_n, hipMemcpyDeviceToDevice,
-                          ctx->stream) == hipSuccess &&
-           hipMemcpyAsync(ok, ctx->comb_ok, ctx->comb_n, hipMemcpyDeviceToDevice, ctx->stream) == hipSuccess &&
-           hipStreamSynchronize(ctx->stream) == hipSuccess;
-  if (!good) {
-    if (rows) (void)hipFree(rows);
-    if (ok) (void)hipFree(ok);
-    comb_drop(ctx);
-    return;
-  }
-  if (ctx->comb) (void)hipFree(ctx->comb);
-  if (ctx->comb_ok) (void)hipFree(ctx->comb_ok);
-  ctx->comb = rows;
-  ctx->comb_ok = ok;
-  ctx->comb_cap = want;
-}
-
-// rows of the table's keys [comb_n, min(table_n, comb_cap)), in batches that bound the
-// builder's workspace (15 Jacobian entries per key, freed afterwards)
-static void comb_build_new(bls_gpu_ctx* ctx, uint32_t table_n) {
-  if (ctx->comb_off || !ctx->comb) return;
-  const uint32_t end = table_n < ctx->comb_cap ? table_n : ctx->comb_cap;
-  if (end <= ctx->comb_n) return;
+// rows and comb_ok of the keys [from, to) of a generation, in batches that bound the
+// builder's workspace (15 Jacobian entries per key, freed afterwards); false: give the
+// comb up (PkTable::append)
+static bool comb_build(bls_gpu_ctx* ctx, const PkGen& gen, uint32_t from, uint32_t to) {
   const uint32_t BATCH = 1u << 16;
-  const uint32_t todo = end - ctx->comb_n;
+  const uint32_t todo = to - from;
+  const G1A* table = (const G1A*)gen.table_p();
+  Fp* comb = (Fp*)gen.comb_p();
   G1J* tmp = nullptr;
   bool good = hipMalloc(&tmp, sizeof(G1J) * G1_COMB_ROWS * (size_t)(todo < BATCH ? todo : BATCH)) == hipSuccess;
-  for (uint32_t at = ctx->comb_n; good && at < end; at += BATCH) {
-    const uint32_t m = end - at < BATCH ? end - at : BATCH;
-    good = launch_k_comb_build(ctx->table + at, m, tmp, ctx->comb + (size_t)G1_COMB_WORDS * at, ctx->comb_ok + at,
+  for (uint32_t at = from; good && at < to; at += BATCH) {
+    const uint32_t m = to - at < BATCH ? to - at : BATCH;
+    good = launch_k_comb_build(table + at, m, tmp, comb + (size_t)G1_COMB_WORDS * at, gen.comb_ok_p() + at,
                                ctx->stream) == hipSuccess;
   }
   good = good && hipStreamSynchronize(ctx->stream) == hipSuccess;
   if (tmp) (void)hipFree(tmp);
-  if (!good) {
-    comb_drop(ctx);
-    return;
-  }
-  ctx->comb_n = end;
+  if (!good) (void)hipGetLastError();
+  return good;
 }
 
+// The load runs on the calling context's stream and workspace, under its table's loader
+// mutex (PkTable::append: decode, wait, rows, wait, and only then the new size for every
+// context that shares the table).
 int64_t bls_gpu_load_pubkeys(bls_gpu_ctx* ctx, const uint8_t* pks, uint32_t n, uint32_t pk_len, int32_t* codes) {
   CTX_LOCK(ctx);
   if (pk_len != 48 && pk_len != 96) {
@@ -732,42 +728,91 @@ int64_t bls_gpu_load_pubkeys(bls_gpu_ctx* ctx, const uint8_t* pks, uint32_t n, u
     return -1;
   }
   HIPC(ctx, hipSetDevice(ctx->device));
-  if (ctx->table_n + n > ctx->table_cap) {
-    uint32_t cap = (ctx->table_n + n) + (ctx->table_n + n) / 2 + 1024;
-    G1A* t = nullptr;
-    HIPC(ctx, hipMalloc(&t, sizeof(G1A) * (size_t)cap));
-    if (ctx->table) {
-      HIPC(ctx, hipMemcpyAsync(t, ctx->table, sizeof(G1A) * (size_t)ctx->table_n, hipMemcpyDeviceToDevice,
-                               ctx->stream));
-      HIPC(ctx, hipStreamSynchronize(ctx->stream));
-      HIPC(ctx, hipFree(ctx->table));
-    }
-    ctx->table = t;
-    ctx->table_cap = cap;
-    comb_grow(ctx, cap);
-  }
-  if (n == 0) return ctx->table_n;
-  size_t in_bytes = (size_t)pk_len * n;
-  Carver cv{nullptr, 0};
-  cv.take<uint8_t>(in_bytes);
-  cv.take<int32_t>(n);
-  if (ensure_dev(ctx, cv.off) || ensure_host(ctx, cv.off)) return -1;
-  Carver c2{ctx->dev_ws, 0};
-  uint8_t* d_in = c2.take<uint8_t>(in_bytes);
-  int32_t* d_codes = c2.take<int32_t>(n);
-  HIPC(ctx, hipMemcpyAsync(d_in, pks, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-  HIPC(ctx, launch_k_load_pubkeys(d_in, n, pk_len, ctx->table + ctx->table_n, d_codes, ctx->stream));
-  std::vector<int32_t> host_codes(n);
-  HIPC(ctx, hipMemcpyAsync(host_codes.data(), d_codes, sizeof(int32_t) * n, hipMemcpyDeviceToHost, ctx->stream));
-  HIPC(ctx, hipStreamSynchronize(ctx->stream));
-  if (codes) memcpy(codes, host_codes.data(), sizeof(int32_t) * n);
+  const size_t in_bytes = (size_t)pk_len * n;
   // all or nothing: a key that does not decode leaves the table as it was, so table
-  // indices (validator indices) stay aligned across contexts and calls
-  for (uint32_t i = 0; i < n; ++i)
-    if (host_codes[i] != 0) return ctx->table_n;
-  comb_build_new(ctx, ctx->table_n + n);
-  ctx->table_n += n;
-  return ctx->table_n;
+  // indices (validator indices) stay aligned across calls
+  auto decode = [&](uint8_t* dst) -> int {
+    Carver cv{nullptr, 0};
+    cv.take<uint8_t>(in_bytes);
+    cv.take<int32_t>(n);
+    if (ensure_dev(ctx, cv.off) || ensure_host(ctx, cv.off)) return -2;
+    Carver c2{ctx->dev_ws, 0};
+    uint8_t* d_in = c2.take<uint8_t>(in_bytes);
+    int32_t* d_codes = c2.take<int32_t>(n);
+    std::vector<int32_t> host_codes(n);
+    HIPC(ctx, hipMemcpyAsync(d_in, pks, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIPC(ctx, launch_k_load_pubkeys(d_in, n, pk_len, (G1A*)dst, d_codes, ctx->stream));
+    HIPC(ctx, hipMemcpyAsync(host_codes.data(), d_codes, sizeof(int32_t) * n, hipMemcpyDeviceToHost, ctx->stream));
+    HIPC(ctx, hipStreamSynchronize(ctx->stream));
+    if (codes) memcpy(codes, host_codes.data(), sizeof(int32_t) * n);
+    for (uint32_t i = 0; i < n; ++i)
+      if (host_codes[i] != 0) return 1;
+    return 0;
+  };
+  auto build = [&](const PkGen& gen, uint32_t from, uint32_t to) { return comb_build(ctx, gen, from, to); };
+  bool decode_err = false;  // (the decode left its own message)
+  auto decode_step = [&](uint8_t* dst) {
+    const int rc = decode(dst);
+    decode_err = rc < 0;
+    return rc;
+  };
+  const char* what = "load";
+  const int64_t r = (*ctx->pkt)->append(n, pk_comb_max_keys(), ctx->stream, decode_step, build, &what);
+  if (r < 0 && !decode_err) {
+    (void)hipGetLastError();
+    snprintf(ctx->err, sizeof(ctx->err), "bls_gpu_load_pubkeys: %s failed", what);
+  }
+  return r;
+}
+
+// ctx leaves its (empty) table for the one `with` uses.  Both contexts' mutexes are held
+// (std::lock: two opposite calls do not deadlock), so neither has a call in flight and
+// neither's table pointer moves meanwhile.
+extern "C" int bls_gpu_share_pubkeys(bls_gpu_ctx* ctx, bls_gpu_ctx* with) {
+  if (!ctx || !with || ctx == with) {
+    if (ctx) {
+      CTX_LOCK(ctx);
+      snprintf(ctx->err, sizeof(ctx->err), "bls_gpu_share_pubkeys: %s",
+               with ? "a context cannot share with itself" : "no context to share with");
+    }
+    return -2;
+  }
+  std::shared_ptr<PkTable> old;  // released after the mutexes
+  {
+    std::unique_lock<std::mutex> a(*ctx->mu, std::defer_lock), b(*with->mu, std::defer_lock);
+    std::lock(a, b);
+    if (*ctx->pkt == *with->pkt) return 0;
+    if (ctx->device != with->device) {
+      snprintf(ctx->err, sizeof(ctx->err), "bls_gpu_share_pubkeys: the contexts are on devices %d and %d",
+               ctx->device, with->device);
+      return -2;
+    }
+    const uint32_t held = (*ctx->pkt)->size();
+    if (held != 0) {
+      snprintf(ctx->err, sizeof(ctx->err), "bls_gpu_share_pubkeys: the context already holds %u keys", held);
+      return -2;
+    }
+    (*ctx->pkt)->detach();
+    old = std::move(*ctx->pkt);
+    *ctx->pkt = *with->pkt;
+    (*ctx->pkt)->attach();
+  }
+  (void)hipSetDevice(ctx->device);
+  old.reset();
+  return 0;
+}
+
+extern "C" int bls_gpu_pubkeys_info(bls_gpu_ctx* ctx, bls_pubkeys_info* out) {
+  if (!ctx || !out) return -2;
+  CTX_LOCK(ctx);
+  const PkInfo i = (*ctx->pkt)->info();
+  out->table_id = i.table_id;
+  out->n_keys = i.n_keys;
+  out->capacity = i.capacity;
+  out->comb_keys = i.comb_keys;
+  out->n_contexts = i.n_contexts;
+  out->device_bytes = i.device_bytes;
+  return 0;
 }
 
 int bls_gpu_validate_pubkeys(bls_gpu_ctx* ctx, const uint8_t* pks, uint32_t n, uint32_t pk_len, int32_t* codes) {
@@ -1059,6 +1104,8 @@ struct PassArgs {
   // verify_deposits: the caller's arrays.  The batch of such a pass is n one-set batchable
   // requests with neither keys nor messages on the host: k_deposit makes both
   const bls_deposit_batch* dep;
+  // the call's snapshot of the pubkey table (nullptr for a deposit call: no table)
+  const PkView* pk;
 };
 
 // Every decision and count of a pass, fixed by plan_pass before anything is staged.
@@ -1354,14 +1401,16 @@ struct VerifyPass {
     b.n_sets = sh.n;
     b.n_reqs = sh.R;
     b.n_chunks = sh.n_chunks;
-    b.pk_table = ctx->table;
-    b.pk_table_n = ctx->table_n;
-    if (ctx->comb && !(ctx->debug_flags & BLS_DEBUG_NO_PK_COMB)) {
-      b.pk_comb = ctx->comb;
-      b.pk_comb_ok = ctx->comb_ok;
-      b.pk_comb_n = ctx->comb_n;
+    if (a.pk) {
+      b.pk_table = a.pk->table();
+      b.pk_table_n = a.pk->snap.n;
+      if (a.pk->comb() && !(ctx->debug_flags & BLS_DEBUG_NO_PK_COMB)) {
+        b.pk_comb = a.pk->comb();
+        b.pk_comb_ok = a.pk->comb_ok();
+        b.pk_comb_n = a.pk->snap.comb_n;
+      }
     }
-    if (!(ctx->debug_flags & BLS_DEBUG_NO_PK_COMB)) b.g1_comb = ctx->g1_comb;
+    if (!(ctx->debug_flags & BLS_DEBUG_NO_PK_COMB)) b.g1_comb = (const Fp*)(*ctx->pkt)->g1_comb();
     b.scalar_base = a.scalar_base;
     b.pack = sh.pack;
     b.mlf_pl = sh.mlf_pl;
@@ -2025,10 +2074,15 @@ static int verify_impl(bls_gpu_ctx* ctx, const bls_batch* in, int32_t* verdicts,
                        const SameMsgPlan* sm = nullptr, const bls_deposit_batch* dep = nullptr) {
   CTX_LOCK(ctx);
   ctx->wait_block = wait_blocks(in->n_sets);
+  // the table as this call sees it: kept until the stream is idle (every stage of a pass
+  // that ran to its end has waited; one that failed part-way is waited for below), so a
+  // load through another context never frees a buffer under this call's kernels
+  PkView pk;
+  if (!dep) pk = pk_snapshot(ctx);
   const int rc = verify_body(ctx, in, PassArgs{verdicts, stats, scalar_base, partial_out, partial_status, partial_err,
-                                               req_bounds, sm, dep});
+                                               req_bounds, sm, dep, dep ? nullptr : &pk});
+  if (rc != 0) (void)hipStreamSynchronize(ctx->stream);
   if (rc < 0 && ctx->msm_state) {
-    (void)hipStreamSynchronize(ctx->stream);
     (void)hipMemsetAsync(ctx->msm_state, 0, sizeof(uint32_t) * MSM_STATE_WORDS, ctx->stream);
     (void)hipStreamSynchronize(ctx->stream);
   }
@@ -2250,9 +2304,17 @@ int bls_gpu_aggregate_pubkeys(bls_gpu_ctx* ctx, const uint32_t* set_pk_offsets, 
   Carver c{ctx->dev_ws, 0};
   carve(c, d_out);
   b.n_sets = n_sets;
-  b.pk_table = ctx->table;
-  b.pk_table_n = ctx->table_n;
+  const PkView pk = pk_snapshot(ctx);  // dropped at return; an error path waits first (below)
+  b.pk_table = pk.table();
+  b.pk_table_n = pk.snap.n;
   hipStream_t s = ctx->stream;
+  struct Drain {  // a failed copy or launch leaves earlier kernels on the stream
+    hipStream_t s;
+    bool armed;
+    ~Drain() {
+      if (armed) (void)hipStreamSynchronize(s);
+    }
+  } drain{s, true};
   HIPC(ctx, hipMemcpyAsync((void*)b.set_pk_off, set_pk_offsets, sizeof(uint32_t) * (n_sets + 1),
                            hipMemcpyHostToDevice, s));
   HIPC(ctx, hipMemcpyAsync((void*)b.pk_idx, pk_indices, sizeof(uint32_t) * n_idx, hipMemcpyHostToDevice, s));
@@ -2267,6 +2329,7 @@ int bls_gpu_aggregate_pubkeys(bls_gpu_ctx* ctx, const uint32_t* set_pk_offsets, 
   HIPC(ctx, hipMemcpyAsync(out96, d_out, 96ull * n_sets, hipMemcpyDeviceToHost, s));
   if (codes) HIPC(ctx, hipMemcpyAsync(codes, b.pk_status, sizeof(int32_t) * n_sets, hipMemcpyDeviceToHost, s));
   HIPC(ctx, hipStreamSynchronize(s));
+  drain.armed = false;
   return 0;
 }
 

@@ -296,6 +296,23 @@ class GpuContext:
         self._check(rc, "bls_gpu_load_pubkeys")
         return codes[:n]
 
+    def share_pubkeys(self, other: "GpuContext") -> None:
+        """Use `other`'s key table instead of a replica of one's own (bls_gpu_share_pubkeys):
+        this context must hold no keys and sit on the same device; afterwards a load through
+        either context appends for both."""
+        if not isinstance(other, GpuContext) or not other._h:
+            raise NativeError("share_pubkeys: the other context is not open")
+        self._check(self.lib.bls_gpu_share_pubkeys(self._h, other._h), "bls_gpu_share_pubkeys")
+
+    def pubkeys_info(self) -> dict:
+        """The key table this context uses (bls_pubkeys_info): table_id (equal for contexts
+        that share a table), n_keys, capacity, comb_keys, n_contexts, device_bytes."""
+        from ._abi import BlsPubkeysInfo
+
+        info = BlsPubkeysInfo()
+        self._check(self.lib.bls_gpu_pubkeys_info(self._h, ctypes.byref(info)), "bls_gpu_pubkeys_info")
+        return {name: int(getattr(info, name)) for name, _ in BlsPubkeysInfo._fields_}
+
     def validate_pubkeys(self, pks: bytes | np.ndarray, pk_len: int = 48) -> np.ndarray:
         """KeyValidate codes (0 valid, else BLST-style code) for n keys (bls_gpu_validate_pubkeys)."""
         arr = _u8(pks)

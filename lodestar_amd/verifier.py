@@ -187,7 +187,8 @@ class GpuBlsVerifier:
     def __init__(self, device: int = 0, n_contexts: int = 2, verify_all_multi_thread: bool = False,
                  max_sets_per_call: int = GPU_SETS_PER_CALL, pubkeys48: bytes | None = None,
                  metrics: BlsMetrics | None = None, devices: Sequence[int] | None = None,
-                 split_call_min_sets: int = SPLIT_CALL_MIN_SETS, context_factory=None, record_calls: bool = False):
+                 split_call_min_sets: int = SPLIT_CALL_MIN_SETS, context_factory=None, record_calls: bool = False,
+                 share_pubkeys: bool = True):
         self.verify_all_multi_thread = verify_all_multi_thread
         self.max_sets_per_call = max_sets_per_call
         self.devices = list(devices) if devices is not None else [device]
@@ -213,6 +214,7 @@ class GpuBlsVerifier:
                 except NativeError as e:
                     self.init_errors.append(e)
         self._main_lock = threading.Lock()
+        self._table_ctxs = self._share_tables() if share_pubkeys else None
         if pubkeys48 is not None:
             self.load_pubkeys(pubkeys48)
         self._cv = threading.Condition()
@@ -243,11 +245,39 @@ class GpuBlsVerifier:
         self._timer.start()
 
     # -- pubkey cache -----------------------------------------------------------
+    def _share_tables(self):
+        """One key table per distinct device id (share_pubkeys, the default): the first
+        context opened on a device -- the main-thread lane on the first -- owns it, every
+        other context there shares it (bls_gpu_share_pubkeys).  Returns the contexts a load
+        goes through, one per device in `devices` order, or None when some context has no
+        share_pubkeys method (an older addon or a stand-in): every context then keeps its
+        own replica, as with share_pubkeys=False."""
+        ctxs = [(self._main, self.devices[0])] + [(c, self.devices[s]) for c, s in zip(self._ctxs, self._ctx_slot)]
+        if not all(callable(getattr(c, "share_pubkeys", None)) for c, _ in ctxs):
+            return None
+        owner: dict = {}
+        for c, dev in ctxs:
+            if dev in owner:
+                c.share_pubkeys(owner[dev])
+            else:
+                owner[dev] = c
+        return list(owner.values())
+
     def load_pubkeys(self, pubkeys48: bytes) -> None:
-        """Append validator pubkeys (48 B compressed) to every context's device table on
-        every device, all or nothing: bls_gpu_load_pubkeys appends no key of a batch that
-        holds an undecodable one, so a failure on the first context leaves every table as
-        it was and validator indices stay aligned across contexts and devices."""
+        """Append validator pubkeys (48 B compressed) to the device table of every device --
+        once per device where its contexts share one table, else context by context -- all
+        or nothing: bls_gpu_load_pubkeys appends no key of a batch that holds an undecodable
+        one, so a failure on the first load leaves every table as it was and validator
+        indices stay aligned across contexts and devices."""
+        if self._table_ctxs is not None:
+            for k, c in enumerate(self._table_ctxs):  # first device first
+                codes = c.load_pubkeys(pubkeys48, 48)
+                if (codes != 0).any():
+                    if k:  # same bytes as on the first device: cannot happen short of a device fault
+                        raise BlsError("pubkey tables diverged across devices")
+                    bad = int((codes != 0).argmax())
+                    raise BlsError(f"invalid pubkey at batch index {bad} (code {int(codes[bad])}); no key appended")
+            return
         first = self._ctxs[0] if self._ctxs else self._main
         codes = first.load_pubkeys(pubkeys48, 48)
         if (codes != 0).any():
