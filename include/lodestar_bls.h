@@ -74,7 +74,8 @@ typedef struct bls_stats {
                                   3 skipped: the context's previous pass failed it, chunks checked straight away */
   uint32_t n_ml_units;         /* Miller-loop units (chunk x shared signing root pairings), 0 = one per set */
   uint32_t pass_shape;         /* how the aggregated path ran (0 on the per-set path): bit 0 the merged signature
-                                  sum by Pippenger MSM; bits 8-15 items per lane of the f side of the Miller loops
+                                  sum by Pippenger MSM, bit 1 its long stages inside the Miller-loop launches
+                                  (0: five launches in front of them); bits 8-15 items per lane of the f side of the Miller loops
                                   (1, 2, 4; 3 = one item per two lanes) */
 } bls_stats;
 
@@ -488,6 +489,11 @@ int bls_gpu_kernel_probe(bls_gpu_ctx* ctx, const char* name, uint32_t lanes, uin
  * key's comb rows exist (bls_gpu_load_pubkeys builds them; $BLS_PK_COMB=0 turns them off
  * for the process), so one process can run the same call through both. */
 #define BLS_DEBUG_NO_PK_COMB 0x10000u
+/* Test / bench hook: the Pippenger signature sum as five launches of its own in front of
+ * the Miller loops (the serial form) also where its long stages would run inside the
+ * Miller-loop launches (pass_shape bit 1; $BLS_MSM_OVERLAP=0 does the same for the
+ * process), so one process can run the same call through both. */
+#define BLS_DEBUG_MSM_SERIAL 0x20000u
 int bls_gpu_set_debug_flags(bls_gpu_ctx* ctx, uint32_t flags);
 
 #ifdef __cplusplus

@@ -100,6 +100,7 @@ DEBUG_MSM = 64
 DEBUG_GROUP_TEST = 128
 DEBUG_MERGED_EVERY_PASS = 0x8000  # (bits 8-9 are BLS_DEBUG_PACK, 12-14 BLS_DEBUG_MLF_PL)
 DEBUG_NO_PK_COMB = 0x10000  # [r] pk by the GLV chain also where the key has comb rows
+DEBUG_MSM_SERIAL = 0x20000  # the Pippenger sum as launches of its own, not inside the Miller-loop launches
 
 
 def DEBUG_MLF_PL(n: int) -> int:

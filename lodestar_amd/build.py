@@ -293,6 +293,13 @@ def build_smsum_host(verbose: bool = True, out: Path | None = None, extra: list[
     return _build_host_program("smsum_host", (), verbose, out, extra)
 
 
+def build_msm_host(verbose: bool = True, out: Path | None = None, extra: list[str] | None = None) -> Path:
+    """CPU restatement of the Pippenger signature sum's stages and of the bucket blocks'
+    tickets (bls/msm.hpp; tests/native/msm_host.cpp), a stand-alone program for tests/; `extra`
+    as above."""
+    return _build_host_program("msm_host", (), verbose, out, extra)
+
+
 def build_plan_host(verbose: bool = True, out: Path | None = None, extra: list[str] | None = None) -> Path:
     """The host-side planners of a verify pass (bls/plan.hpp) run over their edge shapes
     (tests/native/plan_host.cpp), a stand-alone program for tests/; `extra` as above."""
@@ -360,6 +367,7 @@ if __name__ == "__main__":
     build_napi()
     build_hostsim()
     build_smsum_host()
+    build_msm_host()
     build_plan_host()
     build_deposit_host()
     build_comb_host()

@@ -972,6 +972,19 @@ static bool msm_on() {
   return bls_sets_in_flight() > min_sets;
 }
 
+// The overlapped form of the Pippenger sum: its segment, bucket, window and final stages
+// as roles of the first pass's Miller-loop launches (kernels/k_mlq.hip launch_k_mlqf_msm)
+// instead of three launches in front of them.  On unless $BLS_MSM_OVERLAP=0 or the
+// context's BLS_DEBUG_MSM_SERIAL; a pass whose f side is no k_mlf<1> of 1, 2 or 4 items
+// per lane (MLF_PAIR, a forced cooperative packing) keeps the serial form either way.
+static bool msm_overlap_on() {
+  static const bool on = [] {
+    const char* e = getenv("BLS_MSM_OVERLAP");
+    return !(e && atoi(e) == 0);
+  }();
+  return on;
+}
+
 // Shared Miller loops in k_mln (PipeBufs::ml_dom): on unless $BLS_ML_SHARED=0
 static bool ml_shared_on() {
   static const bool on = [] {
@@ -1139,6 +1152,7 @@ struct PassShape {
   // (an MSM entry packs its bucket slot in 22 bits and a bucket takes up to 2 entries per
   // set: passes above MSM_MAX_SETS keep the group sums)
   bool use_msm;
+  bool msm_overlap;  // ... with its long stages inside the Miller-loop launches, if the f-side shape allows
   bool ml_shared;  // k_mln shares one loop among four consecutive live items of one domain
   // f / chain layout: sets [0, n) | chunk signature sums [n, n + C) | units
   // [n + C, n + C + U) | individual requests' signature sums [n + C + U, .. + R)
@@ -1221,6 +1235,7 @@ PassShape plan_pass(const bls_gpu_ctx* ctx, const bls_batch* in, const PassArgs&
   if (sh.use_units && !sh.smsum) plan_gsum_sets(pl.units.goff, pl.units.members, pl.unit_gsum);
   sh.use_total = sh.sigagg && !sh.sm && sh.merged && C > 1 && sig_total_on();
   sh.use_msm = sh.use_total && n <= MSM_MAX_SETS && ((msm_on() && !sh.merged_after_fail) || (flags & BLS_DEBUG_MSM));
+  sh.msm_overlap = sh.use_msm && msm_overlap_on() && !(flags & BLS_DEBUG_MSM_SERIAL);
   if (sh.use_total) {
     std::vector<uint32_t> goff(C + 1, (uint32_t)pl.chunk_gsum.gsets.size());
     goff[0] = 0;
@@ -1281,6 +1296,7 @@ struct VerifyPass {
   // ---- what the stages leave for the later ones
   bool rs_done;          // the per-set RS = [r] sig (chain CH_RS) exist (ensure_rs)
   uint32_t pass_pl = 0;  // the first pass's items per k_mlf lane
+  bool msm_overlapped = false;  // the first pass ran the Pippenger sum inside its Miller-loop launches
   std::vector<int32_t> chunk_ok, merged_status;
   int32_t merged_verdict = 0;
   uint32_t flagged = 0;
@@ -1577,7 +1593,16 @@ struct VerifyPass {
     } else if (sh.use_msm) {
       msm.cnt = ctx->msm_state;
       msm.ticket = ctx->msm_state + MSM_BUCKETS;
-      HIPC(ctx, launch_k_msm(b, msm, sh.n_chunks, sh.n, s)); dbg_sync(s, "k_msm");
+      // the f-side shape (below) also decides the sum's form: the overlapped one rides on
+      // k_mlf<1>'s launch
+      choose_mlf_pl();
+      msm_overlapped = sh.msm_overlap && k_mln_list_ok(b) && (b.mlf_pl == 1 || b.mlf_pl == 2 || b.mlf_pl == 4);
+      if (msm_overlapped) {
+        // the sort alone (it needs chain_live); the rest runs beside the Miller loops
+        HIPC(ctx, launch_k_msm_sort(b, msm, s)); dbg_sync(s, "k_msm sort");
+      } else {
+        HIPC(ctx, launch_k_msm(b, msm, sh.n_chunks, sh.n, s)); dbg_sync(s, "k_msm");
+      }
     } else if (sh.use_total ? launch_gsum(pl.total_gsum, tseg_dev, sh.n) : launch_gsum(pl.chunk_gsum, gseg_dev, sh.n)) {
       return -1;
     }
@@ -1590,9 +1615,22 @@ struct VerifyPass {
       b.gsets = gsets_dev;
     }
     HIPC(ctx, hipEventRecord(ctx->ev[4], s));
-    // the f-side shape is chosen once per call (other contexts change the sets in flight
-    // meanwhile): the first pass's Miller-loop launch and stats->pass_shape use it
-    if (!b.mlf_pl && k_mln_list_ok(b)) b.mlf_pl = mlf_per_lane();
+    choose_mlf_pl();
+    if (msm_overlapped) {
+      // sets and units with the sum's stages on the launches' lowest blocks; the virtual
+      // sets exist when the f-side launch ends.  Only group 0's is live (the others are
+      // written as infinity, f = 1, bls/msm.hpp msm_final_lane), so it alone is paired: one
+      // cooperative wavefront, or the SIMT pair where there is no such program
+      HIPC(ctx, launch_k_mlqf_msm(b, msm, sh.n_chunks, sh.n_units, b.ml_lines, s)); dbg_sync(s, "k_mlqf_msm");
+      hipError_t e = launch_k_mln_coop(b, ctx->coop, sh.n, 1, nullptr, s);
+      if (e == hipErrorNotSupported) {
+        const uint32_t pl_pass = b.mlf_pl;  // (launch_ml_alone picks its own shape)
+        e = launch_ml_alone(sh.n, 1, nullptr);
+        b.mlf_pl = pl_pass;
+      }
+      HIPC(ctx, e); dbg_sync(s, "k_mln sum");
+      return 0;
+    }
     // a same-message call's first pass has two Miller loops per job (its unit and its
     // signature sum) and one per 1-set job: few items that never share f, so they run as
     // the cooperative single-pair loops, one wavefront each (launch_k_mln_coop: ~1 ms
@@ -1610,6 +1648,12 @@ struct VerifyPass {
     if (ml_rc == hipErrorNotSupported) ml_rc = launch_k_mln(b, ctx->coop, 0, sh.indiv_vbase, s);
     HIPC(ctx, ml_rc); dbg_sync(s, "k_mln");
     return 0;
+  }
+
+  // the f-side shape is chosen once per call (other contexts change the sets in flight
+  // meanwhile): the first pass's Miller-loop launch and stats->pass_shape use it
+  void choose_mlf_pl() {
+    if (!b.mlf_pl && k_mln_list_ok(b)) b.mlf_pl = mlf_per_lane();
   }
 
   // Merged check: FE(prod of every f_i) == 1 with one final exponentiation (k_fprod
@@ -1711,7 +1755,9 @@ struct VerifyPass {
     }
     if (a.stats) {
       a.stats->merged_check = sh.merged ? (merged_pass ? 1 : 2) : (sh.merged_skipped ? 3 : 0);
-      a.stats->pass_shape = sh.sigagg ? ((sh.use_msm ? 1u : 0u) | (k_mln_list_ok(b) ? pass_pl << 8 : 0u)) : 0u;
+      a.stats->pass_shape = sh.sigagg ? ((sh.use_msm ? 1u : 0u) | (msm_overlapped ? 2u : 0u) |
+                                         (k_mln_list_ok(b) ? pass_pl << 8 : 0u))
+                                      : 0u;
       a.stats->n_flagged = flagged;
       a.stats->n_unique_msgs = sh.n_uniq;
       a.stats->n_ml_units = sh.n_units;

@@ -30,6 +30,7 @@
 #include <stdlib.h>
 
 #include "../launchers.hpp"
+#include "bls/msm.hpp"
 #include "bls/pairing.hpp"
 
 using namespace bls;
@@ -124,16 +125,22 @@ __device__ __forceinline__ Fp12 ml_f(const uint32_t* L, uint32_t stride, uint32_
   return fp12_conj(f);
 }
 
+// Item k of a launch: items[k] of a list, else first + k, with the items from gap_at on
+// moved up by gap (the overlapped first pass runs the sets and the units and leaves out
+// the chunk groups' virtual sets between them; every other launch has gap = 0).
+struct MlItems {
+  uint32_t first, count, gap_at, gap;
+  const uint32_t* items;
+  __device__ __forceinline__ uint32_t at(uint32_t k) const {
+    return items ? items[k] : first + k + (k >= gap_at ? gap : 0u);
+  }
+};
 
-}  // namespace
-
-template <int W>
-__global__ __launch_bounds__(BLS_BLOCK) __attribute__((amdgpu_waves_per_eu(W, W))) void k_mlq(
-    PipeBufs b, uint32_t first, uint32_t count, uint32_t units_paired, uint32_t* L, uint32_t stride,
-    const uint32_t* items) {
-  const uint32_t k = blockIdx.x * BLS_BLOCK + threadIdx.x;
-  if (k >= count) return;
-  const uint32_t i = items ? items[k] : first + k;
+// the line side of item k (lane k of the launch's Miller-loop blocks)
+__device__ __forceinline__ void mlq_lane(const PipeBufs& b, const MlItems& it, uint32_t k, uint32_t units_paired,
+                                         uint32_t* L, uint32_t stride) {
+  if (k >= it.count) return;
+  const uint32_t i = it.at(k);
   if (!ml_live(b, i, units_paired)) return;
   const Fp* ch = b.chain + (size_t)CHAIN_WORDS * i;
   G1J rp;
@@ -162,34 +169,123 @@ __global__ __launch_bounds__(BLS_BLOCK) __attribute__((amdgpu_waves_per_eu(W, W)
   }
 }
 
-template <int W>
-__global__ __launch_bounds__(BLS_BLOCK) __attribute__((amdgpu_waves_per_eu(W, W))) void k_mlf(
-    PipeBufs b, uint32_t first, uint32_t count, uint32_t units_paired, const uint32_t* L, uint32_t stride,
-    const uint32_t* items, uint32_t per_lane) {
-  // per_lane items k0 .. k0 + per_lane - 1 per lane: when all are live and of one product
-  // domain they share one f (one squaring per bit for all of them), else each runs its
-  // own; items (an index list, the individually verified pass) never share
-  const uint32_t k0 = per_lane * (blockIdx.x * BLS_BLOCK + threadIdx.x);
-  if (k0 >= count) return;
-  const uint32_t n = min(per_lane, count - k0);
-  const uint32_t i0 = items ? items[k0] : first + k0;
+// the f side of lane t: per_lane items k0 .. k0 + per_lane - 1.  When all are live and of
+// one product domain they share one f (one squaring per bit for all of them), else each
+// runs its own; items (an index list, the individually verified pass) never share
+__device__ __forceinline__ void mlf_lane(const PipeBufs& b, const MlItems& it, uint32_t t, uint32_t units_paired,
+                                         const uint32_t* L, uint32_t stride, uint32_t per_lane) {
+  const uint32_t k0 = per_lane * t;
+  if (k0 >= it.count) return;
+  const uint32_t n = min(per_lane, it.count - k0);
+  const uint32_t i0 = it.at(k0);
   // ml_dom covers the first-pass items [0, indiv_vbase) only: the individually verified
   // requests' signature sums after it never share (reading past it paired two requests'
   // sums into one f -- the verdict bug test_verify_many_merged_signature_sum_fails found)
-  bool share = n > 1 && units_paired && b.ml_dom && !items && ml_live(b, i0, units_paired);
+  bool share = n > 1 && units_paired && b.ml_dom && !it.items && ml_live(b, i0, units_paired);
   for (uint32_t g = 1; share && g < n; ++g) {
-    const uint32_t i = first + k0 + g;
+    const uint32_t i = it.at(k0 + g);
     share = ml_live(b, i, units_paired) && i < b.indiv_vbase && b.ml_dom[i] == b.ml_dom[i0];
   }
   if (share) {
     b.f[i0] = ml_f(L, stride, k0, n);
-    for (uint32_t g = 1; g < n; ++g) b.f[first + k0 + g] = fp12_one();
+    for (uint32_t g = 1; g < n; ++g) b.f[it.at(k0 + g)] = fp12_one();
     return;
   }
   for (uint32_t g = 0; g < n; ++g) {
-    const uint32_t i = items ? items[k0 + g] : first + k0 + g;
+    const uint32_t i = it.at(k0 + g);
     if (ml_live(b, i, units_paired)) b.f[i] = ml_f(L, stride, k0 + g, 1);
   }
+}
+
+}  // namespace
+
+template <int W>
+__global__ __launch_bounds__(BLS_BLOCK) __attribute__((amdgpu_waves_per_eu(W, W))) void k_mlq(
+    PipeBufs b, uint32_t first, uint32_t count, uint32_t units_paired, uint32_t* L, uint32_t stride,
+    const uint32_t* items) {
+  mlq_lane(b, MlItems{first, count, 0xFFFFFFFFu, 0u, items}, blockIdx.x * BLS_BLOCK + threadIdx.x, units_paired, L,
+           stride);
+}
+
+template <int W>
+__global__ __launch_bounds__(BLS_BLOCK) __attribute__((amdgpu_waves_per_eu(W, W))) void k_mlf(
+    PipeBufs b, uint32_t first, uint32_t count, uint32_t units_paired, const uint32_t* L, uint32_t stride,
+    const uint32_t* items, uint32_t per_lane) {
+  mlf_lane(b, MlItems{first, count, 0xFFFFFFFFu, 0u, items}, blockIdx.x * BLS_BLOCK + threadIdx.x, units_paired, L,
+           stride, per_lane);
+}
+
+// ---------------------------------------------------------------------------
+// The overlapped form of a first pass that sums its signatures by the Pippenger method
+// (kernels/k_msm.hip, bls/msm.hpp).  Nothing needs the sum before the chunk groups'
+// virtual sets are paired, and the sets' and units' own Miller loops do not depend on it,
+// so the sum's long stages run as roles of these two launches' lowest blocks instead of
+// as three nearly empty launches in front of them (192, 16 and 4 wavefronts, each waiting
+// for a free wave slot among the other passes' 512-register waves):
+//   k_mlq_msm  blocks [0, seg_blocks): k_msm_seg's body, one lane per segment; the blocks
+//              after them: k_mlq's body over the sets [0, n) and the units (MlItems gap:
+//              never the virtual sets [n, n + C), which do not exist yet)
+//   k_mlf_msm  blocks [0, 16): k_msm_bucket's body, four blocks per window; the last of a
+//              window's four to arrive (a ticket per window) runs k_msm_window's body as
+//              its one wavefront, and the last of the four windows (the ticket of the
+//              serial form) sums them and writes the virtual sets; the blocks after them:
+//              k_mlf<1>'s body over the same items as k_mlq_msm
+// The role branches are uniform over a block.  No wavefront waits for another: the only
+// ordering inside a launch is "the last arriver continues", everything else is the order
+// of the launches on the stream (k_mlq_msm's segment sums are complete before k_mlf_msm
+// starts).  The MSM blocks come first in the grid so that they are dispatched first; they
+// raise their priority as the serial kernels do.  LDS per block: the Fp2 primitive's slot
+// (6 KB) + the window's lane array (18 KB) + flags < 25 KB, four blocks (one per SIMD) per
+// CU under 100 KB of its 160 KB.
+// ---------------------------------------------------------------------------
+constexpr uint32_t MSM_BUCKET_BLOCKS = MSM_W * MSM_BKT_BLOCKS;
+// every block of k_mlf_msm is charged the window role's lane array beside the Fp2 slot:
+// four blocks (one wavefront per SIMD) must fit a CU's 160 KB of LDS
+static_assert(4 * (sizeof(G2J) * MSM_LANES + 12 * BLS_FP2_SLOT_LANES * sizeof(uint64_t) + 64) <= 160 * 1024,
+              "k_mlf_msm: LDS per CU no longer holds one wavefront per SIMD");
+
+// The MSM blocks' bodies, out of line: the kernels' own registers and scratch accesses are
+// then the Miller-loop role's, as in k_mlq / k_mlf (inlined, the bucket role cost k_mlf's
+// per-item line loop two more scratch loads and stores per line; profiles/ab_msm_overlap.json)
+static __device__ __attribute__((noinline)) void msm_seg_role(const PipeBufs& b, const MsmBufs& m, uint32_t seg) {
+  BLS_TAIL_PRIO();
+  msm_seg_lane(b, m, seg, blockIdx.x * BLS_BLOCK + threadIdx.x);
+}
+
+static __device__ __attribute__((noinline)) void msm_bucket_role(const PipeBufs& b, const MsmBufs& m, uint32_t groups,
+                                                                 uint32_t vbase) {
+  BLS_TAIL_PRIO();
+  __shared__ G2J lanes[MSM_LANES];
+  const uint32_t w = msm_bucket_block_window(blockIdx.x);
+  msm_bucket_block_lane(m, blockIdx.x, threadIdx.x);
+  if (!msm_last_block(m.ticket + 2 + w, MSM_BKT_BLOCKS)) return;
+  msm_window_wave(m, w, lanes);
+  if (!msm_last_block(m.ticket + 1, MSM_W)) return;
+  msm_final_lane(b, m, threadIdx.x, groups, vbase);
+}
+
+template <int W>
+__global__ __launch_bounds__(BLS_BLOCK) __attribute__((amdgpu_waves_per_eu(W, W))) void k_mlq_msm(
+    PipeBufs b, MsmBufs m, uint32_t seg, uint32_t seg_blocks, uint32_t count, uint32_t gap_at, uint32_t gap,
+    uint32_t* L, uint32_t stride) {
+  if (blockIdx.x < seg_blocks) {
+    msm_seg_role(b, m, seg);
+    return;
+  }
+  mlq_lane(b, MlItems{0u, count, gap_at, gap, nullptr}, (blockIdx.x - seg_blocks) * BLS_BLOCK + threadIdx.x, 1u, L,
+           stride);
+}
+
+template <int W>
+__global__ __launch_bounds__(BLS_BLOCK) __attribute__((amdgpu_waves_per_eu(W, W))) void k_mlf_msm(
+    PipeBufs b, MsmBufs m, uint32_t count, uint32_t gap_at, uint32_t gap, const uint32_t* L, uint32_t stride,
+    uint32_t per_lane) {
+  if (blockIdx.x < MSM_BUCKET_BLOCKS) {
+    msm_bucket_role(b, m, gap, gap_at);  // the gap is the chunk groups' virtual sets
+    return;
+  }
+  mlf_lane(b, MlItems{0u, count, gap_at, gap, nullptr}, (blockIdx.x - MSM_BUCKET_BLOCKS) * BLS_BLOCK + threadIdx.x,
+           1u, L, stride, per_lane);
 }
 
 // ---------------------------------------------------------------------------
@@ -290,6 +386,20 @@ hipError_t launch_k_mlqf(const PipeBufs& b, uint32_t first, uint32_t count, bool
   }
   const uint32_t lanes = (count + per_lane - 1) / per_lane;
   k_mlf<1><<<bls_grid_for(lanes), BLS_BLOCK, 0, s>>>(b, first, count, up, lines, stride, items, per_lane);
+  return hipGetLastError();
+}
+
+hipError_t launch_k_mlqf_msm(const PipeBufs& b, const MsmBufs& m, uint32_t groups, uint32_t n_units, uint32_t* lines,
+                             hipStream_t s) {
+  const uint32_t n = b.n_sets, count = n + n_units, per_lane = b.mlf_pl;
+  if (n == 0 || groups == 0 || !(per_lane == 1 || per_lane == 2 || per_lane == 4)) return hipErrorInvalidValue;
+  const uint32_t stride = (count + BLS_BLOCK - 1) / BLS_BLOCK * BLS_BLOCK;
+  const uint32_t seg_blocks = bls_grid_for((uint32_t)msm_seg_cap(n));
+  k_mlq_msm<1><<<seg_blocks + bls_grid_for(count), BLS_BLOCK, 0, s>>>(b, m, msm_seg_len(n), seg_blocks, count, n,
+                                                                      groups, lines, stride);
+  const uint32_t lanes = (count + per_lane - 1) / per_lane;
+  k_mlf_msm<1><<<MSM_BUCKET_BLOCKS + bls_grid_for(lanes), BLS_BLOCK, 0, s>>>(b, m, count, n, groups, lines, stride,
+                                                                            per_lane);
   return hipGetLastError();
 }
 

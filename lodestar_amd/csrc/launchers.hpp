@@ -37,27 +37,31 @@ hipError_t launch_k_exact(const bls::PipeBufs& b, hipStream_t s);
 // roles: bit k runs k_chain role k (0 H, 1 subgroup, 2 [r] sig, 3 [r] pk); k_chain_done
 // follows unless only role 2 runs (the merged check's fallback needs the per-set RS)
 hipError_t launch_k_chain(const bls::PipeBufs& b, hipStream_t s, uint32_t roles = 0xFu);
-// Pippenger sum of [r_i] sig_i over the live sets (kernels/k_msm.hip)
-struct MsmBufs {
-  uint32_t* cnt;      // 1020 bucket counts + 2 tickets: per context, zero between passes
-  uint32_t* ticket;   // cnt + 1020
-  uint32_t* off;      // 1021 bucket offsets into sorted
-  uint32_t* seg_off;  // 1021 segment offsets
-  uint32_t* ent;      // 8 n_sets (bucket << 22 | slot) entries
-  uint32_t* sorted;   // 8 n_sets point references in bucket order
-  bls::G2J* seg_sum;  // msm_seg_cap(n_sets)
-  bls::G2J* bucket;   // 1020
-  bls::G2J* win;      // 4
-};
+// Pippenger sum of [r_i] sig_i over the live sets (kernels/k_msm.hip; stage bodies in bls/msm.hpp)
+#include "bls/msm_bufs.hpp"
+using bls::MsmBufs;
 #define MSM_BUCKETS 1020u
 size_t msm_seg_cap(uint32_t n_sets);
-#define MSM_STATE_WORDS (MSM_BUCKETS + 2u)
+// bucket counts, then the tickets: k_msm_bin's, the windows', one per window's bucket blocks
+#define MSM_STATE_WORDS (MSM_BUCKETS + 6u)
+static_assert(MSM_BUCKETS == bls::MSM_NB && MSM_STATE_WORDS == bls::MSM_NB + bls::MSM_TICKETS, "bls/msm_bufs.hpp");
 // k_msm_bin: 22-bit bucket slots, <= 2 entries per set and bucket
 #define MSM_MAX_SETS (1u << 21)
 // mlf_per_lane(): one item per TWO f lanes (kernels/k_mlq.hip k_mlf2)
 #define MLF_PAIR 3u
-// the merged signature sum into the chunk groups' virtual sets vbase .. vbase + groups
+// the merged signature sum into the chunk groups' virtual sets vbase .. vbase + groups:
+// the serial form, five launches
 hipError_t launch_k_msm(const bls::PipeBufs& b, const MsmBufs& m, uint32_t groups, uint32_t vbase, hipStream_t s);
+// ... and its first two alone (k_msm_bin, k_msm_scatter) for the overlapped form
+hipError_t launch_k_msm_sort(const bls::PipeBufs& b, const MsmBufs& m, hipStream_t s);
+// The overlapped form (kernels/k_mlq.hip): the first pass's Miller loops of the sets
+// [0, n_sets) and the units [n_sets + groups, n_sets + groups + n_units) in k_mlq's and
+// k_mlf<1>'s bodies, with the sum's segment stage on the lowest blocks of the line-side
+// launch and its bucket, window and final stages on the lowest 16 blocks of the f-side
+// launch; the virtual sets n_sets .. n_sets + groups exist when the f-side launch ends (the
+// caller pairs them after it).  b.mlf_pl = 1, 2 or 4 (hipErrorInvalidValue otherwise).
+hipError_t launch_k_mlqf_msm(const bls::PipeBufs& b, const MsmBufs& m, uint32_t groups, uint32_t n_units,
+                             uint32_t* lines, hipStream_t s);
 hipError_t launch_k_gsum(const bls::PipeBufs& b, const uint32_t* seg, uint32_t n_seg, const bls::G2J* in,
                          bls::G2J* out, hipStream_t s);
 hipError_t launch_k_vset(const bls::PipeBufs& b, const bls::G2J* sums, uint32_t n_groups, uint32_t vbase,
