@@ -2,7 +2,9 @@
 // no HIP, no context, no environment.  bls_gpu.hip stages what these functions return and
 // the kernels index memory through it, so each plan is also checked on the CPU
 // (tests/native/plan_exports.hpp, tests/test_plan_cpu.py, and under sanitizers
-// tests/native/plan_host.cpp).  Whatever selects a variant comes in as a parameter.
+// tests/native/plan_host.cpp).  Whatever selects a variant comes in as a parameter; at the
+// end plan_pass, the decision table of a whole pass, takes the parsed knobs (bls/knobs.hpp)
+// the same way.
 #pragma once
 
 #include <stdint.h>
@@ -12,6 +14,7 @@
 #include <vector>
 
 #include "../../../include/lodestar_bls.h"
+#include "knobs.hpp"
 #include "plan_shape.hpp"
 
 namespace bls {
@@ -560,6 +563,173 @@ inline size_t grp_cap(uint32_t R, uint32_t C) { return (size_t)R + 14ull * C + 2
 inline size_t grp_mem_cap(uint32_t R) { return 8ull * R + 16; }
 inline bool group_tests_fit(const GroupTestsA& a, uint32_t R, uint32_t C) {
   return a.members.size() <= grp_mem_cap(R) && a.off.size() - 1 <= grp_cap(R, C);
+}
+
+// ---- the pass ---------------------------------------------------------------------------
+
+// what the entry point asks of the pass ...
+struct PassAsk {
+  bool partial;            // the Miller-loop partial of one shard (bls_gpu_partial)
+  const SameMsgPlan* sm;   // verify_same_message: its own plan
+  bool dep;                // a deposit call: n one-set batchable requests, keys and roots made on the device
+  const std::vector<uint32_t>* req_bounds;  // verify_many: the messages' first requests
+};
+
+// ... and what its context and process contribute
+struct PassEnv {
+  uint32_t debug_flags;     // bls_gpu_set_debug_flags
+  bool last_merged_failed;  // the context's last pass failed its merged check
+  uint64_t in_flight;       // sets in the verify calls now running in this process, this call's included
+};
+
+// Every decision and count of a pass, fixed by plan_pass before anything is staged.
+struct PassShape {
+  uint32_t n, R, n_chunks, n_uniq, n_pk_idx;
+  bool partial, sm, dedup;
+  bool dep;  // a deposit call (PassAsk::dep)
+  // Merged check: with only batchable requests and >= 2 chunks, first test the product of
+  // every f_i with ONE final exponentiation (k_fprod tree); it passes iff every chunk would
+  // (the same random-scalar batch, just larger), so chunk_ok is all 1 and the per-chunk
+  // final exponentiations are skipped.  A failing merged check (or a request with an error
+  // status) falls back to k_chunk_coop, so verdicts and stats stay those of the chunked
+  // worker (worker.ts:56-88).  merged_skipped: Knobs::merged_skip_after_fail.
+  bool merged_eligible, merged_skipped, merged;
+  // aggregated-signature path (a same-message call always: the per-set k_pset path would
+  // bring back one Miller loop pair per set)
+  bool sigagg;
+  bool use_units;  // Miller-loop units; same-message jobs: one per job, whatever the flags
+  bool smsum;      // ... and their sums of r_i pk_i and r_i sig_i by k_smsum, one wavefront per job
+  // Merged signature sum: under the merged check the chunks' signature sums only ever meet
+  // in the product of every f, and prod_c e(-g1, S_c) = e(-g1, sum_c S_c) after the final
+  // exponentiation, so the first pass sums every chunk's r_i sig_i into ONE point (chunk
+  // group 0; the other chunk groups are empty, so k_vset gives them f = 1) and pairs it
+  // once.  A failing merged check re-sums per chunk and pairs each sum before the
+  // per-chunk final exponentiations, so chunk verdicts are unchanged.  (Not for
+  // same-message jobs: each job's sum is paired in the first pass's launch.)
+  bool use_total;
+  // ... and under it the sum is one Pippenger MSM over the live sets (kernels/k_msm.hip)
+  // instead of per-set [r] sig chains + k_gsum levels; the per-set RS are made (k_chain
+  // role 2 alone) only when the merged check fails and the chunks' own sums are needed
+  // (an MSM entry packs its bucket slot in 22 bits and a bucket takes up to 2 entries per
+  // set: passes above MSM_MAX_SETS keep the group sums)
+  bool use_msm;
+  bool msm_overlap;  // ... with its long stages inside the Miller-loop launches, if the f-side shape allows
+  bool ml_shared;  // k_mln shares one loop among four consecutive live items of one domain
+  // f / chain layout: sets [0, n) | chunk signature sums [n, n + C) | units
+  // [n + C, n + C + U) | individual requests' signature sums [n + C + U, .. + R)
+  uint32_t n_units, unit_base, indiv_vbase, n_total;
+  uint32_t n_prod;  // the f's of every set, chunk group and unit: what the product trees multiply
+  // group tests: the smallest chunk tested so, whether any chunk is that large (their
+  // buffers are carved only then), $BLS_GROUP_EQ, the fewest group-tested requests that
+  // take group sums (SIZE_MAX: never)
+  uint32_t gt_min;
+  bool gt_possible;
+  int gt_eq_mode;
+  size_t gsums_min;
+  // SIMT final exponentiations (kernels/k_fin_simt.hip) for a failing pass's many chunk
+  // checks / requests verified alone: 4 Fp12 per task, carved when a pass could need them.
+  // fe_min: the task count from which they run one lane per task ($BLS_FE_SIMT_MIN;
+  // default 0 = off: at 256 the cfg4 per-set-request slice ran 1.04M vs 1.15M sets/s steady
+  // and the cfg5 slice 2.56M vs 2.83M -- a lane's ~8k dependent Fp products take ~8 ms, and
+  // those passes wait on the tail's latency, not on device time; profiles/r06_ab_fe_simt.json)
+  uint32_t fe_min;
+  bool fe_simt_possible;
+  uint32_t init_set_flag, pack, mlf_pl;  // BLS_DEBUG_FORCE_EXACT, _PACK, _MLF_PL
+  bool pl_forced;                        // a test forces the items per k_mlf lane
+  bool merged_after_fail;                // the context's last pass failed its merged check
+  size_t gseg_cap, gtmp_cap, grp_cap, grp_mem_cap;
+};
+
+// the host vectors a pass stages with its inputs
+struct PassPlans {
+  BatchPlan built;  // unless the caller brought its own (same-message calls)
+  const BatchPlan* plan;
+  std::vector<uint32_t> msg_uniq, msg_rep;
+  UnitPlan units;
+  GsumPlan chunk_gsum, unit_gsum, total_gsum;
+  std::vector<uint32_t> ml_dom;
+  std::vector<uint32_t> agg_list;  // aggregate sets big enough for a wavefront each (k_pk_agg)
+};
+
+// The decision table of a pass: from what the call asks, what its context contributes and
+// the process's knobs (bls/knobs.hpp) it fills the plans and returns the shape.  Nothing
+// else reads a debug flag, a knob that shapes the pass or the merged-check history.
+inline PassShape plan_pass(const bls_batch* in, const PassAsk& a, const PassEnv& env, const Knobs& k,
+                           PassPlans& pl) {
+  PassShape sh;
+  memset(&sh, 0, sizeof(sh));
+  const uint32_t flags = env.debug_flags;
+  const uint32_t n = sh.n = in->n_sets, R = sh.R = in->n_reqs;
+  const uint32_t* req_off = in->req_set_offsets;
+  sh.partial = a.partial;
+  sh.sm = a.sm != nullptr;
+  sh.dep = a.dep;
+  if (a.sm) {
+    pl.plan = &a.sm->plan;  // every job a caller-defined chunk (plan_same_message)
+  } else {
+    if (a.req_bounds) plan_batch_msgs(in, *a.req_bounds, pl.built);
+    else plan_batch(in, pl.built);
+    pl.plan = &pl.built;
+  }
+  const BatchPlan& plan = *pl.plan;
+  // (a deposit call's roots are made on the device: nothing to dedup on the host)
+  const bool no_dedup = sh.dep || (flags & BLS_DEBUG_NO_MSG_DEDUP);
+  sh.n_uniq = no_dedup ? n : plan_msg_dedup(in->messages, n, pl.msg_uniq, pl.msg_rep);
+  sh.dedup = sh.n_uniq < n;
+  // (same-message and deposit calls neither read nor write the context's merged-check
+  // history: invalid deposits are normal and must not shape the next gossip pass)
+  sh.merged_after_fail = !sh.dep && env.last_merged_failed;
+  sh.merged_eligible = !sh.partial && plan.chunk_off.size() > 2 && plan.nonbatch_reqs.empty() && n > 0 &&
+                       !(flags & BLS_DEBUG_NO_MERGED_CHECK);
+  sh.merged_skipped = sh.merged_eligible && !sh.sm && sh.merged_after_fail && k.merged_skip_after_fail &&
+                      !(flags & BLS_DEBUG_MERGED_EVERY_PASS);
+  sh.merged = sh.merged_eligible && !sh.merged_skipped;
+  const uint32_t C = sh.n_chunks = (uint32_t)plan.chunk_off.size() - 1;
+  sh.n_pk_idx = in->set_pk_offsets ? in->set_pk_offsets[n] : 0;
+  sh.sigagg = n > 0 && (sh.sm || use_sigagg(k, flags, n, env.in_flight));
+  if (sh.sm && C > 0) units_same_message(plan, pl.msg_rep, n, pl.units);
+  sh.use_units = sh.sm ? C > 0
+                       : sh.sigagg && sh.dedup && !(flags & BLS_DEBUG_NO_UNITS) &&
+                             plan_units(req_off, plan, pl.msg_rep, n, pl.units);
+  sh.smsum = sh.sm && sh.use_units;
+  sh.n_units = sh.use_units ? pl.units.n_units : 0;
+  sh.unit_base = n + C;
+  sh.indiv_vbase = n + C + sh.n_units;
+  sh.n_total = sh.sigagg ? sh.indiv_vbase + R : n;
+  sh.n_prod = sh.sigagg ? sh.indiv_vbase : n;
+  // the chunk groups' sum plan is staged with the inputs
+  if (sh.sigagg && !sh.smsum) plan_gsum(req_off, plan.chunk_off, plan.chunk_reqs, pl.chunk_gsum);
+  if (sh.use_units && !sh.smsum) plan_gsum_sets(pl.units.goff, pl.units.members, pl.unit_gsum);
+  sh.use_total = sh.sigagg && !sh.sm && sh.merged && C > 1 && k.sig_total;
+  sh.use_msm = sh.use_total && n <= MSM_MAX_SETS &&
+               ((msm_on(k, env.in_flight) && !sh.merged_after_fail) || (flags & BLS_DEBUG_MSM));
+  sh.msm_overlap = sh.use_msm && k.msm_overlap && !(flags & BLS_DEBUG_MSM_SERIAL);
+  if (sh.use_total) {
+    std::vector<uint32_t> goff(C + 1, (uint32_t)pl.chunk_gsum.gsets.size());
+    goff[0] = 0;
+    plan_gsum_sets(goff, pl.chunk_gsum.gsets, pl.total_gsum);
+  }
+  sh.gseg_cap = gseg_cap(n, R);
+  sh.gtmp_cap = gtmp_cap(n, R);
+  sh.ml_shared = sh.sigagg && k.ml_shared;
+  if (sh.ml_shared) plan_ml_domains(req_off, plan, sh.use_units ? &pl.units : nullptr, n, pl.ml_dom);
+  if (in->set_pk_offsets)
+    for (uint32_t i = 0; i < n; ++i)
+      if (in->set_pk_offsets[i + 1] - in->set_pk_offsets[i] >= BLS_AGG_WAVE_MIN) pl.agg_list.push_back(i);
+  sh.fe_min = k.fe_simt_min;
+  sh.fe_simt_possible = sh.fe_min > 0 && (C >= sh.fe_min || R >= sh.fe_min);
+  sh.gt_min = group_test_min(k, flags);
+  for (uint32_t ch = 0; ch < C && !sh.gt_possible; ++ch)
+    sh.gt_possible = plan.chunk_off[ch + 1] - plan.chunk_off[ch] >= sh.gt_min;
+  sh.grp_cap = sh.gt_possible ? grp_cap(R, C) : 0;
+  sh.grp_mem_cap = sh.gt_possible ? grp_mem_cap(R) : 0;
+  sh.gt_eq_mode = k.group_eq;
+  sh.gsums_min = group_sums_min(k);
+  sh.init_set_flag = (flags & BLS_DEBUG_FORCE_EXACT) ? 1u : 0u;
+  sh.pack = (flags & BLS_DEBUG_PACK_MASK) >> 8;
+  sh.mlf_pl = (flags & BLS_DEBUG_MLF_PL_MASK) >> 12;
+  sh.pl_forced = (flags & BLS_DEBUG_MLF_PL_MASK) != 0;
+  return sh;
 }
 
 // ---- verdicts -----------------------------------------------------------------------------

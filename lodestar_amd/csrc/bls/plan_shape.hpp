@@ -9,3 +9,8 @@
 // GroupBufs::ref[g]: REF_CHUNK | c = compare with chunk c's checked value ref_fe[c]
 #define REF_CHUNK 0x80000000u
 #define REF_NONE 0xFFFFFFFFu  // no comparison (the chunk indices stay far below 2^31 - 1)
+#define BLS_AGG_WAVE_MIN 16u  // aggregate sets of at least this many keys: k_pk_agg
+// k_msm_bin: 22-bit bucket slots, <= 2 entries per set and bucket
+#define MSM_MAX_SETS (1u << 21)
+// items per k_mlf lane (bls/knobs.hpp mlf_per_lane): one item per TWO f lanes (kernels/k_mlq.hip k_mlf2)
+#define MLF_PAIR 3u

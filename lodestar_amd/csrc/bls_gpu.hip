@@ -4,8 +4,9 @@
 // the CPU test harness); cooperative programs from tools/gen_coop.py.
 //
 // Every verify entry point (bls_gpu_verify, _verify_many, _verify_same_message, _partial,
-// _verify_deposits) is one VerifyPass (below): plan_pass fixes its shape and plans, then verify_body calls
-// its stages in order.  The inputs sit in pinned mapped staging memory (no H2D copy), all
+// _verify_deposits) is one VerifyPass (below): plan_pass (bls/plan.hpp) fixes its shape and plans from the
+// process's knobs (bls/knobs.hpp: the BLS_* variables and the decisions taken from them),
+// then verify_body calls its stages in order.  The inputs sit in pinned mapped staging memory (no H2D copy), all
 // kernels run on the context's stream, and the host waits after the first pass and after
 // each fallback round.
 //   k_pk, k_pre   pubkey decode / table aggregation; SSWU points of H(m), signature decode
@@ -53,6 +54,7 @@
 
 #include "bls/deposit.hpp"
 #include "bls/group_decode.hpp"
+#include "bls/knobs.hpp"
 #include "bls/pk_table.hpp"
 #include "bls/plan.hpp"
 #include "launchers.hpp"
@@ -838,39 +840,10 @@ int bls_gpu_validate_pubkeys(bls_gpu_ctx* ctx, const uint8_t* pks, uint32_t n, u
   return 0;
 }
 
-// Which first pass a call takes.  Aggregated-signature path (k_chain + k_gsum + k_vset + k_mln single-pair Miller
-// loops, one signature Miller loop per chunk) from SIGAGG_MIN_SETS sets on, except for
-// calls of at most PERSET_MAX_CALL sets while the process has at most
-// $BLS_PERSET_MAX_INFLIGHT (20,480) sets in flight (this call's included): those run the
-// all-cooperative k_pset / k_psetn (a set's chains spread over a wavefront instead of one
-// lane: shorter calls while the device has room, fewer sets per second once it is full --
-// per-set vs aggregated at 12 x 1024-set calls in flight 0.82M vs 0.56M sets/s, 16 x 1024
-// 0.82M vs 0.72M, 24 x 1024 1.02M vs 1.03M, profiles/r04_ab_perset_crossover.json).  A call of more sets would fill
-// every SIMD with its wavefronts (2 sets each, two per SIMD) and hold the main-thread
-// lane's context behind it (test_napi.py: a 4096-set pool call finished first).
-// BLS_DEBUG_SIGAGG_ON / _OFF or $BLS_SIGAGG (0 / 1) force a path.
-#define SIGAGG_MIN_SETS 512u
-#define PERSET_MAX_CALL 2048u
-static bool use_sigagg(const bls_gpu_ctx* ctx, uint32_t n) {
-  static const int env = [] {
-    const char* e = getenv("BLS_SIGAGG");
-    return e ? atoi(e) : -1;
-  }();
-  static const uint64_t perset_max = [] {
-    const char* e = getenv("BLS_PERSET_MAX_INFLIGHT");
-    return e ? (uint64_t)strtoull(e, nullptr, 10) : 20480ull;
-  }();
-  if (ctx->debug_flags & BLS_DEBUG_SIGAGG_ON) return true;
-  if (ctx->debug_flags & BLS_DEBUG_SIGAGG_OFF) return false;
-  if (env >= 0) return env != 0;
-  return n >= SIGAGG_MIN_SETS && (n > PERSET_MAX_CALL || bls_sets_in_flight() > perset_max);
-}
-
 // $BLS_DEBUG_SYNC: synchronise after every kernel of a verify call and log its name
 // and wall time to stderr (a kernel that never finishes is the last name printed)
 static void dbg_sync(hipStream_t s, const char* what) {
-  static const bool on = getenv("BLS_DEBUG_SYNC") != nullptr;
-  if (!on) return;
+  if (!knobs().debug_sync) return;
   timespec t0, t1;
   clock_gettime(CLOCK_MONOTONIC, &t0);
   fprintf(stderr, "[bls sync] %s ...", what);
@@ -882,168 +855,12 @@ static void dbg_sync(hipStream_t s, const char* what) {
   fflush(stderr);
 }
 
-// Group testing of a failed chunk's requests (instead of one final exponentiation per
-// request, worker.ts:91-98).  Each request's product F_t (its sets' f and, on the
-// aggregated path, its own signature-sum pairing) is left by k_indiv_coop; a test is
-// FE(prod of a group's F_t) == 1 (k_group_coop), the same random-scalar batch check the
-// reference runs over a chunk.  With the chunk's requests of status OK indexed 0 .. m-1:
-//   pass A: the group of all of them (A), and for each bit j of the index the group G_j
-//           of those with bit j set; each G_j's final exponentiation is also compared with
-//           A's (k_group_cmp): FE(G_j) FE(rest_j) = FE(A), so FE(rest_j) == 1 iff
-//           FE(G_j) == FE(A) -- every test answers for its complement too;
-//   a single invalid request b fails exactly one of G_j, rest_j for every j (G_j where
-//   b's bit j is set), which names b, and every other request sits in a passing test;
-//   pass C: any other outcome (both of some G_j, rest_j failing: two or more invalid; an
-//           index past m): every request alone.
-// With one invalid request in a chunk of 16 that is 5 final exponentiations in one round
-// instead of 16 (round 6; before it, without the comparison, pass B tested {b} alone and
-// the rest together: 6 in two rounds, $BLS_GROUP_EQ=0 restores that); verdicts and the worker counters are the reference's (a test that passes is the
-// batch the reference's retry would have passed request by request, with the same
-// soundness).  On for chunks of >= 4 requests since round 6: once the failed chunks'
-// requests stopped re-running their sets' own Miller loops and the chunks of a failing
-// stream are checked without the merged check first, the saved final exponentiations
-// outweigh the extra rounds -- cfg4 per-set requests 1.35M -> 1.50M sets/s steady, cfg5
-// level (profiles/r06_ab_group_test.json; in rounds 4-5 it lost or was level,
-// r04_ab_group_test.json, r05_ab_group_test_again.json).  $BLS_GROUP_TEST_MIN sets the
-// smallest chunk tested so (0 = off); BLS_DEBUG_GROUP_TEST forces chunks of >= 4.
-static uint32_t group_test_min(const bls_gpu_ctx* ctx) {
-  static const uint32_t v = [] {
-    const char* e = getenv("BLS_GROUP_TEST_MIN");
-    const long x = e ? atol(e) : 4;
-    return x <= 0 ? 0xFFFFFFFFu : (uint32_t)(x < 2 ? 2 : x);
-  }();
-  return (ctx->debug_flags & BLS_DEBUG_GROUP_TEST) ? 4u : v;
-}
-
-// group sums (VerifyPass::group_sums) for a pass with at least $BLS_GROUP_SUMS_MIN (512)
-// group-tested requests; 0 = always, $BLS_GROUP_SUMS=0 = never (SIZE_MAX).  They save Miller loops
-// (cfg4 per-set requests, ~1,300 group-tested requests a pass: 1.52M -> 1.56M sets/s
-// steady) but put a sum + Miller-loop stage in front of each round of tests, where the
-// per-request sums ride in the requests' Miller-loop launch: with a few failed chunks
-// a pass (the cfg5 slice, ~80 requests) that latency costs more (3.29M -> 3.05M)
-// (profiles/r06_ab_group_sums.json)
-static size_t group_sums_min() {
-  static const bool on = [] {
-    const char* e = getenv("BLS_GROUP_SUMS");
-    return !(e && atoi(e) == 0);
-  }();
-  static const size_t min_reqs = [] {
-    const char* e = getenv("BLS_GROUP_SUMS_MIN");
-    return e ? (size_t)strtoull(e, nullptr, 10) : (size_t)512;
-  }();
-  return on ? min_reqs : SIZE_MAX;
-}
-
-// complement inference in the group tests (verify_groups): pass A carries each chunk's
-// test of all its requests and compares the bit groups' final exponentiations with it, so
-// one invalid request is found without pass B ({b} alone, the rest together); the whole's
-// value is the failed chunk check's own final exponentiation where that ran over the same
-// requests (k_chunk_coop keeps it in b.chunk_fe), else a test of them.  $BLS_GROUP_EQ=0
-// restores the two rounds, =2 always tests the whole
-static int group_eq_mode() {
-  static const int mode = [] {
-    const char* e = getenv("BLS_GROUP_EQ");
-    return e ? atoi(e) : 1;
-  }();
-  return mode;
-}
-
-// Pippenger merged signature sum (k_msm) instead of the per-set [r] sig chains (k_chain
-// role 2, ~1.6k Fp products per set) and the k_gsum levels: ~10 % fewer instructions per
-// set, but its serial stages (segments, buckets, the windows' dependent additions) make
-// the pass ~5 ms longer.  So it pays only when the device is VALU-bound with many sets in
-// flight: 3.46M vs 3.21M sets/s at 16 x 16, level at 12 x 16, 1.89M vs 2.25M at 4 x 16
-// (profiles/r03_ab_msm.json, round 3).  On the round-5 build it is level at 4 x 16 and
-// ahead from 6 x 16 on (8 x 16: 3.24M / 3.30M vs 3.00M, profiles/r05_ab_msm_min.json), so
-// by default on while the process has more than $BLS_MSM_MIN (60,000) sets in flight and
-// the context's last pass passed its merged check (a failing pass needs the per-set chains
-// after all: relaunching them cost the epoch slice with invalid sets 2.42M -> 2.1M sets/s);
-// $BLS_MSM=1 / 0 forces it on / off.
-static bool msm_on() {
-  static const int forced = [] {
-    const char* e = getenv("BLS_MSM");
-    return e && (e[0] == '0' || e[0] == '1') ? e[0] - '0' : -1;
-  }();
-  static const uint64_t min_sets = [] {
-    const char* e = getenv("BLS_MSM_MIN");
-    return e ? (uint64_t)strtoull(e, nullptr, 10) : 60000ull;
-  }();
-  if (forced >= 0) return forced == 1;
-  return bls_sets_in_flight() > min_sets;
-}
-
-// The overlapped form of the Pippenger sum: its segment, bucket, window and final stages
-// as roles of the first pass's Miller-loop launches (kernels/k_mlq.hip launch_k_mlqf_msm)
-// instead of three launches in front of them.  On unless $BLS_MSM_OVERLAP=0 or the
-// context's BLS_DEBUG_MSM_SERIAL; a pass whose f side is no k_mlf<1> of 1, 2 or 4 items
-// per lane (MLF_PAIR, a forced cooperative packing) keeps the serial form either way.
-static bool msm_overlap_on() {
-  static const bool on = [] {
-    const char* e = getenv("BLS_MSM_OVERLAP");
-    return !(e && atoi(e) == 0);
-  }();
-  return on;
-}
-
-// Shared Miller loops in k_mln (PipeBufs::ml_dom): on unless $BLS_ML_SHARED=0
-static bool ml_shared_on() {
-  static const bool on = [] {
-    const char* e = getenv("BLS_ML_SHARED");
-    return !(e && atoi(e) == 0);
-  }();
-  return on;
-}
-
-// Merged signature sum (with the merged check): one signature Miller loop per device
-// pass instead of one per chunk; on unless $BLS_SIG_TOTAL=0
-static bool sig_total_on() {
-  static const bool on = [] {
-    const char* e = getenv("BLS_SIG_TOTAL");
-    return !(e && atoi(e) == 0);
-  }();
-  return on;
-}
-
-// After a pass whose merged check failed, a context's next pass skips it and checks its
-// chunks straight away (each chunk's own signature sum paired in the pass's Miller-loop
-// launch, then the per-chunk final exponentiations): a stream with invalid sets in most
-// passes (the cfg4 per-set requests, the cfg5 epoch slice) otherwise pays the merged
-// final exponentiation, then the chunk sums, their Miller loops and the chunk checks one
-// after another on the failing call's path.  The first pass whose chunks all pass turns
-// the merged check back on.  $BLS_MERGED_AFTER_FAIL=1 keeps it on every pass.
-static bool merged_skip_after_fail() {
-  static const bool on = [] {
-    const char* e = getenv("BLS_MERGED_AFTER_FAIL");
-    return !(e && atoi(e) == 1);
-  }();
-  return on;
-}
-
 struct InFlight {
   uint64_t n;
   explicit InFlight(uint64_t k) : n(k) { g_sets_in_flight.fetch_add(n, std::memory_order_relaxed); }
   ~InFlight() { g_sets_in_flight.fetch_sub(n, std::memory_order_relaxed); }
 };
 
-// How the verify path's host thread waits for its stream.  hipStreamSynchronize spins
-// (so does hipEventSynchronize on a hipEventBlockingSync event in this runtime): with 16
-// contexts each waiting through a ~95 ms pass the process held ~15.7 CPUs and the job's
-// 16-CPU quota throttled it (profiles/r06_ab_sync_wait.json) -- CPU a beacon node's main
-// thread and its other work need.  A pass of more than 2,048 sets (only the aggregated
-// path takes those; tens of ms) polls an event with 50 us sleeps instead; smaller calls
-// keep the spin: they can take the per-set path, a few ms, where polling at 1024-set
-// calls cost 4 x 1 calls 7.2 -> 7.8 ms.  $BLS_SYNC=spin / poll forces either.
-static int sync_mode() {
-  static const int m = [] {
-    const char* e = getenv("BLS_SYNC");
-    return e && !strcmp(e, "spin") ? 1 : e && !strcmp(e, "poll") ? 2 : 0;
-  }();
-  return m;
-}
-static bool wait_blocks(uint32_t n_sets) {
-  const int m = sync_mode();
-  return m == 2 || (m == 0 && n_sets > 2048);
-}
 static hipError_t pass_wait(bls_gpu_ctx* ctx, hipStream_t s) {
   if (!ctx->wait_block || s != ctx->stream) return hipStreamSynchronize(s);
   hipError_t e = hipEventRecord(ctx->ev_wait, s);
@@ -1121,149 +938,6 @@ struct PassArgs {
   const PkView* pk;
 };
 
-// Every decision and count of a pass, fixed by plan_pass before anything is staged.
-struct PassShape {
-  uint32_t n, R, n_chunks, n_uniq, n_pk_idx;
-  bool partial, sm, dedup;
-  bool dep;  // a deposit call (PassArgs::dep)
-  // Merged check: with only batchable requests and >= 2 chunks, first test the product of
-  // every f_i with ONE final exponentiation (k_fprod tree); it passes iff every chunk would
-  // (the same random-scalar batch, just larger), so chunk_ok is all 1 and the per-chunk
-  // final exponentiations are skipped.  A failing merged check (or a request with an error
-  // status) falls back to k_chunk_coop, so verdicts and stats stay those of the chunked
-  // worker (worker.ts:56-88).  merged_skipped: merged_skip_after_fail.
-  bool merged_eligible, merged_skipped, merged;
-  // aggregated-signature path (a same-message call always: the per-set k_pset path would
-  // bring back one Miller loop pair per set)
-  bool sigagg;
-  bool use_units;  // Miller-loop units; same-message jobs: one per job, whatever the flags
-  bool smsum;      // ... and their sums of r_i pk_i and r_i sig_i by k_smsum, one wavefront per job
-  // Merged signature sum: under the merged check the chunks' signature sums only ever meet
-  // in the product of every f, and prod_c e(-g1, S_c) = e(-g1, sum_c S_c) after the final
-  // exponentiation, so the first pass sums every chunk's r_i sig_i into ONE point (chunk
-  // group 0; the other chunk groups are empty, so k_vset gives them f = 1) and pairs it
-  // once.  A failing merged check re-sums per chunk and pairs each sum before the
-  // per-chunk final exponentiations, so chunk verdicts are unchanged.  (Not for
-  // same-message jobs: each job's sum is paired in the first pass's launch.)
-  bool use_total;
-  // ... and under it the sum is one Pippenger MSM over the live sets (kernels/k_msm.hip)
-  // instead of per-set [r] sig chains + k_gsum levels; the per-set RS are made (k_chain
-  // role 2 alone) only when the merged check fails and the chunks' own sums are needed
-  // (an MSM entry packs its bucket slot in 22 bits and a bucket takes up to 2 entries per
-  // set: passes above MSM_MAX_SETS keep the group sums)
-  bool use_msm;
-  bool msm_overlap;  // ... with its long stages inside the Miller-loop launches, if the f-side shape allows
-  bool ml_shared;  // k_mln shares one loop among four consecutive live items of one domain
-  // f / chain layout: sets [0, n) | chunk signature sums [n, n + C) | units
-  // [n + C, n + C + U) | individual requests' signature sums [n + C + U, .. + R)
-  uint32_t n_units, unit_base, indiv_vbase, n_total;
-  uint32_t n_prod;  // the f's of every set, chunk group and unit: what the product trees multiply
-  // group tests: the smallest chunk tested so, whether any chunk is that large (their
-  // buffers are carved only then), $BLS_GROUP_EQ, the fewest group-tested requests that
-  // take group sums (SIZE_MAX: never)
-  uint32_t gt_min;
-  bool gt_possible;
-  int gt_eq_mode;
-  size_t gsums_min;
-  // SIMT final exponentiations (kernels/k_fin_simt.hip) for a failing pass's many chunk
-  // checks / requests verified alone: 4 Fp12 per task, carved when a pass could need them
-  uint32_t fe_min;
-  bool fe_simt_possible;
-  uint32_t init_set_flag, pack, mlf_pl;  // BLS_DEBUG_FORCE_EXACT, _PACK, _MLF_PL
-  bool pl_forced;                        // a test forces the items per k_mlf lane
-  bool merged_after_fail;                // the context's last pass failed its merged check
-  size_t gseg_cap, gtmp_cap, grp_cap, grp_mem_cap;
-};
-
-// the host vectors a pass stages with its inputs (bls/plan.hpp)
-struct PassPlans {
-  BatchPlan built;  // unless the caller brought its own (same-message calls)
-  const BatchPlan* plan;
-  std::vector<uint32_t> msg_uniq, msg_rep;
-  UnitPlan units;
-  GsumPlan chunk_gsum, unit_gsum, total_gsum;
-  std::vector<uint32_t> ml_dom;
-  std::vector<uint32_t> agg_list;  // aggregate sets big enough for a wavefront each (k_pk_agg)
-};
-
-// The one place a pass reads the environment knobs, the context's debug flags and its
-// merged-check history: fills the plans and returns the shape.
-PassShape plan_pass(const bls_gpu_ctx* ctx, const bls_batch* in, const PassArgs& a, PassPlans& pl) {
-  PassShape sh;
-  memset(&sh, 0, sizeof(sh));
-  const uint32_t flags = ctx->debug_flags;
-  const uint32_t n = sh.n = in->n_sets, R = sh.R = in->n_reqs;
-  const uint32_t* req_off = in->req_set_offsets;
-  sh.partial = a.partial_out != nullptr;
-  sh.sm = a.sm != nullptr;
-  sh.dep = a.dep != nullptr;
-  if (a.sm) {
-    pl.plan = &a.sm->plan;  // every job a caller-defined chunk (plan_same_message)
-  } else {
-    if (a.req_bounds) plan_batch_msgs(in, *a.req_bounds, pl.built);
-    else plan_batch(in, pl.built);
-    pl.plan = &pl.built;
-  }
-  const BatchPlan& plan = *pl.plan;
-  // (a deposit call's roots are made on the device: nothing to dedup on the host)
-  const bool no_dedup = sh.dep || (flags & BLS_DEBUG_NO_MSG_DEDUP);
-  sh.n_uniq = no_dedup ? n : plan_msg_dedup(in->messages, n, pl.msg_uniq, pl.msg_rep);
-  sh.dedup = sh.n_uniq < n;
-  // (same-message and deposit calls neither read nor write the context's merged-check
-  // history: invalid deposits are normal and must not shape the next gossip pass)
-  sh.merged_after_fail = !sh.dep && ctx->last_merged_failed;
-  sh.merged_eligible = !sh.partial && plan.chunk_off.size() > 2 && plan.nonbatch_reqs.empty() && n > 0 &&
-                       !(flags & BLS_DEBUG_NO_MERGED_CHECK);
-  sh.merged_skipped = sh.merged_eligible && !sh.sm && sh.merged_after_fail && merged_skip_after_fail() &&
-                      !(flags & BLS_DEBUG_MERGED_EVERY_PASS);
-  sh.merged = sh.merged_eligible && !sh.merged_skipped;
-  const uint32_t C = sh.n_chunks = (uint32_t)plan.chunk_off.size() - 1;
-  sh.n_pk_idx = in->set_pk_offsets ? in->set_pk_offsets[n] : 0;
-  sh.sigagg = n > 0 && (sh.sm || use_sigagg(ctx, n));
-  if (sh.sm && C > 0) units_same_message(plan, pl.msg_rep, n, pl.units);
-  sh.use_units = sh.sm ? C > 0
-                       : sh.sigagg && sh.dedup && !(flags & BLS_DEBUG_NO_UNITS) &&
-                             plan_units(req_off, plan, pl.msg_rep, n, pl.units);
-  sh.smsum = sh.sm && sh.use_units;
-  sh.n_units = sh.use_units ? pl.units.n_units : 0;
-  sh.unit_base = n + C;
-  sh.indiv_vbase = n + C + sh.n_units;
-  sh.n_total = sh.sigagg ? sh.indiv_vbase + R : n;
-  sh.n_prod = sh.sigagg ? sh.indiv_vbase : n;
-  // the chunk groups' sum plan is staged with the inputs
-  if (sh.sigagg && !sh.smsum) plan_gsum(req_off, plan.chunk_off, plan.chunk_reqs, pl.chunk_gsum);
-  if (sh.use_units && !sh.smsum) plan_gsum_sets(pl.units.goff, pl.units.members, pl.unit_gsum);
-  sh.use_total = sh.sigagg && !sh.sm && sh.merged && C > 1 && sig_total_on();
-  sh.use_msm = sh.use_total && n <= MSM_MAX_SETS && ((msm_on() && !sh.merged_after_fail) || (flags & BLS_DEBUG_MSM));
-  sh.msm_overlap = sh.use_msm && msm_overlap_on() && !(flags & BLS_DEBUG_MSM_SERIAL);
-  if (sh.use_total) {
-    std::vector<uint32_t> goff(C + 1, (uint32_t)pl.chunk_gsum.gsets.size());
-    goff[0] = 0;
-    plan_gsum_sets(goff, pl.chunk_gsum.gsets, pl.total_gsum);
-  }
-  sh.gseg_cap = gseg_cap(n, R);
-  sh.gtmp_cap = gtmp_cap(n, R);
-  sh.ml_shared = sh.sigagg && ml_shared_on();
-  if (sh.ml_shared) plan_ml_domains(req_off, plan, sh.use_units ? &pl.units : nullptr, n, pl.ml_dom);
-  if (in->set_pk_offsets)
-    for (uint32_t i = 0; i < n; ++i)
-      if (in->set_pk_offsets[i + 1] - in->set_pk_offsets[i] >= BLS_AGG_WAVE_MIN) pl.agg_list.push_back(i);
-  sh.fe_min = fe_simt_min();
-  sh.fe_simt_possible = sh.fe_min > 0 && (C >= sh.fe_min || R >= sh.fe_min);
-  sh.gt_min = group_test_min(ctx);
-  for (uint32_t ch = 0; ch < C && !sh.gt_possible; ++ch)
-    sh.gt_possible = plan.chunk_off[ch + 1] - plan.chunk_off[ch] >= sh.gt_min;
-  sh.grp_cap = sh.gt_possible ? grp_cap(R, C) : 0;
-  sh.grp_mem_cap = sh.gt_possible ? grp_mem_cap(R) : 0;
-  sh.gt_eq_mode = group_eq_mode();
-  sh.gsums_min = group_sums_min();
-  sh.init_set_flag = (flags & BLS_DEBUG_FORCE_EXACT) ? 1u : 0u;
-  sh.pack = (flags & BLS_DEBUG_PACK_MASK) >> 8;
-  sh.mlf_pl = (flags & BLS_DEBUG_MLF_PL_MASK) >> 12;
-  sh.pl_forced = (flags & BLS_DEBUG_MLF_PL_MASK) != 0;
-  return sh;
-}
-
 // One verify call's pass over the device: shape and plans fixed at construction, buffers
 // carved by stage_inputs, then the stages in the order verify_body calls them.  Every
 // stage returns 0 or the call's error code (ctx->err set).
@@ -1309,7 +983,10 @@ struct VerifyPass {
   GsumPlan indiv_gsum;
 
   VerifyPass(bls_gpu_ctx* c, const bls_batch* batch, const PassArgs& args)
-      : ctx(c), in(batch), a(args), s(c->stream), sh(plan_pass(c, batch, args, pl)), plan(*pl.plan),
+      : ctx(c), in(batch), a(args), s(c->stream),
+        sh(plan_pass(batch, PassAsk{args.partial_out != nullptr, args.sm, args.dep != nullptr, args.req_bounds},
+                     PassEnv{c->debug_flags, c->last_merged_failed, bls_sets_in_flight()}, knobs(), pl)),
+        plan(*pl.plan),
         rs_done(!sh.use_msm), chunk_ok(sh.n_chunks + 1, 0), merged_status(sh.merged ? sh.R : 0, 0) {
     memset(&b, 0, sizeof(b));
     memset(&g, 0, sizeof(g));
@@ -1634,13 +1311,13 @@ struct VerifyPass {
     // a same-message call's first pass has two Miller loops per job (its unit and its
     // signature sum) and one per 1-set job: few items that never share f, so they run as
     // the cooperative single-pair loops, one wavefront each (launch_k_mln_coop: ~1 ms
-    // where the SIMT pair takes ~7 ms), while they fit coop_ml_max()
+    // where the SIMT pair takes ~7 ms), while they fit $BLS_COOP_ML_MAX
     hipError_t ml_rc = hipErrorNotSupported;
     if (sh.sm && k_mln_list_ok(b) && !sh.pl_forced) {
       std::vector<uint32_t> items(plan.nonbatch_reqs);
       for (uint32_t ch = 0; ch < sh.n_chunks; ++ch) items.push_back(sh.n + ch);
       for (uint32_t u = 0; u < sh.n_units; ++u) items.push_back(sh.unit_base + u);
-      if (items.size() <= coop_ml_max()) {
+      if (items.size() <= knobs().coop_ml_max) {
         stage_vec(own_sets_dev, items);
         ml_rc = launch_k_mln_coop(b, ctx->coop, 0, (uint32_t)items.size(), own_sets_dev, s);
       }
@@ -1653,7 +1330,7 @@ struct VerifyPass {
   // the f-side shape is chosen once per call (other contexts change the sets in flight
   // meanwhile): the first pass's Miller-loop launch and stats->pass_shape use it
   void choose_mlf_pl() {
-    if (!b.mlf_pl && k_mln_list_ok(b)) b.mlf_pl = mlf_per_lane();
+    if (!b.mlf_pl && k_mln_list_ok(b)) b.mlf_pl = mlf_per_lane(knobs(), bls_sets_in_flight());
   }
 
   // Merged check: FE(prod of every f_i) == 1 with one final exponentiation (k_fprod
@@ -1703,10 +1380,10 @@ struct VerifyPass {
   // the Miller-loop launches after the first pass take their own items-per-lane
   // (mlf_per_lane_alone: their items never share f) unless a test forces one
   void alone_pl(uint32_t count) {
-    const uint32_t pl_alone = mlf_per_lane_alone(count);
+    const uint32_t pl_alone = mlf_per_lane_alone(knobs(), count);
     if (pl_alone && !sh.pl_forced && k_mln_list_ok(b)) b.mlf_pl = pl_alone;
   }
-  // ... and up to coop_ml_max() items they are cooperative single-pair loops, one
+  // ... and up to $BLS_COOP_ML_MAX items they are cooperative single-pair loops, one
   // wavefront per item (launch_k_mln_coop), else the SIMT pair at that shape
   hipError_t launch_ml_alone(uint32_t first, uint32_t count, const uint32_t* items) {
     if (count == 0) return hipSuccess;
@@ -1996,7 +1673,7 @@ struct VerifyPass {
   }
 };
 
-// Group tests of the failed chunks iv.gt_chunks (the comment above group_test_min): pass A
+// Group tests of the failed chunks iv.gt_chunks (the comment above group_test_min, bls/knobs.hpp): pass A
 // (bls/plan.hpp plan_group_tests_a), its decode (bls/group_decode.hpp, or pass B without
 // complement inference), pass C for what is left; verdicts into indiv_verdict.
 int VerifyPass::verify_groups() {
@@ -2119,7 +1796,7 @@ static int verify_impl(bls_gpu_ctx* ctx, const bls_batch* in, int32_t* verdicts,
                        uint32_t* partial_err = nullptr, const std::vector<uint32_t>* req_bounds = nullptr,
                        const SameMsgPlan* sm = nullptr, const bls_deposit_batch* dep = nullptr) {
   CTX_LOCK(ctx);
-  ctx->wait_block = wait_blocks(in->n_sets);
+  ctx->wait_block = wait_blocks(knobs(), in->n_sets);
   // the table as this call sees it: kept until the stream is idle (every stage of a pass
   // that ran to its end has waited; one that failed part-way is waited for below), so a
   // load through another context never frees a buffer under this call's kernels

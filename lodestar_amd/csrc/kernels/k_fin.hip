@@ -12,6 +12,7 @@
 #define BLS_FP_D28 1  // 28-bit-digit Montgomery product (bls/field.hpp)
 #include "../launchers.hpp"
 #include "../bls/coop.hpp"
+#include "../bls/knobs.hpp"
 
 using namespace bls;
 
@@ -283,11 +284,7 @@ __global__ __launch_bounds__(2 * COOP_LANES) void k_indiv_coop2(PipeBufs b, cons
 // Up to $BLS_INDIV2_MAX (64) requests verified alone: two wavefronts each (k_indiv_coop2);
 // more: one (the rate of a failing pass's many requests)
 hipError_t launch_k_indiv_coop(const PipeBufs& b, const CoopEnv& env, const GroupBufs& g, hipStream_t s) {
-  static const uint32_t w2_max = [] {
-    const char* e = getenv("BLS_INDIV2_MAX");
-    return e ? (uint32_t)strtoul(e, nullptr, 10) : 64u;
-  }();
-  if (b.n_indiv <= w2_max && env.fin_fe2_w2.n > 0) k_indiv_coop2<<<b.n_indiv, 2 * COOP_LANES, 0, s>>>(b, env.dev, g);
+  if (b.n_indiv <= bls::knobs().indiv2_max && env.fin_fe2_w2.n > 0) k_indiv_coop2<<<b.n_indiv, 2 * COOP_LANES, 0, s>>>(b, env.dev, g);
   else k_indiv_coop<<<b.n_indiv, COOP_LANES, 0, s>>>(b, env.dev, g);
   return hipGetLastError();
 }

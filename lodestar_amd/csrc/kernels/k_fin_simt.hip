@@ -16,8 +16,6 @@
 // cooperative form stays the choice for a few tasks, whose latency is the call's
 // (launch_k_chunk_fe / launch_k_indiv_fe pick by the task count, $BLS_FE_SIMT_MIN).
 #define BLS_FP_D28 1
-#include <stdlib.h>
-
 #include "../launchers.hpp"
 #include "bls/pairing.hpp"
 
@@ -146,19 +144,6 @@ __global__ __launch_bounds__(BLS_BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1)
     return;
   }
   b.indiv_verdict[t] = fe_is_one(F, save + 4ull * t) ? 1 : 0;
-}
-
-// the task count from which a failing pass's final exponentiations run one lane per
-// task ($BLS_FE_SIMT_MIN; default 0 = off: at 256 the cfg4 per-set-request slice ran
-// 1.04M vs 1.15M sets/s steady and the cfg5 slice 2.56M vs 2.83M -- a lane's ~8k
-// dependent Fp products take ~8 ms, and those passes wait on the tail's latency, not on
-// device time; profiles/r06_ab_fe_simt.json)
-uint32_t fe_simt_min() {
-  static const uint32_t v = [] {
-    const char* e = getenv("BLS_FE_SIMT_MIN");
-    return e ? (uint32_t)strtoul(e, nullptr, 10) : 0u;
-  }();
-  return v;
 }
 
 // save: 4 Fp12 per task (chunks / requests)

@@ -30,6 +30,7 @@
 #include <stdlib.h>
 
 #include "../launchers.hpp"
+#include "bls/knobs.hpp"
 #include "bls/msm.hpp"
 #include "bls/pairing.hpp"
 
@@ -361,26 +362,11 @@ hipError_t launch_k_mlqf(const PipeBufs& b, uint32_t first, uint32_t count, bool
   // +3 % at 12 x 16 over two per SIMD, profiles/r03_ab_mlq_mlf.json)
   const uint32_t up = (own_only || items) ? 0u : 1u;
   k_mlq<1><<<bls_grid_for(count), BLS_BLOCK, 0, s>>>(b, first, count, up, lines, stride, items);
-  // Items per k_mlf lane: 2 shares f's squarings between two pairs (fewer instructions:
-  // the rate when the device is VALU-bound), 1 halves the f chain (the rate when few sets
-  // are in flight and the pass latency sets it): 2.22M vs 2.00M sets/s with 64k sets in
-  // flight, 2.76M vs 2.90M with 128k (profiles/r03_ab_mlq_mlf.json).  By default the
-  // process's sets in flight (every context's verify call, bls_sets_in_flight) pick:
-  // 2 above $BLS_MLF_PL2_MIN (default 98,304) sets, 4 above $BLS_MLF_PL4_MIN (200,000:
-  // 3.55M vs 3.41M sets/s at 12 x 22), else 1.  $BLS_MLF_PER_LANE = 1, 2, 4 or 3 (MLF_PAIR)
-  // fixes it.  (Four items sharing f per lane PAIR, the squarings and line products split
-  // over the pair, lost 6-11 %: spills and ~9 % more lane work, profiles/r06_ab_mlf_pair4.json.)
-  // Up to $BLS_MLF_PAIR_MAX (16,384) sets in flight: two lanes per item (k_mlf2, MLF_PAIR;
-  // at two waves per SIMD, $BLS_MLF2_WAVES=1 for one): a solo pass's f side 4.7 vs 7.1 ms
-  // at 8,192 sets, 5.2 vs 7.2 ms at 16,384, but 8.8 vs 7.4 ms at 32,768
-  // (profiles/r04_ab_mlf_pair.json).
-  const uint32_t per_lane = b.mlf_pl ? b.mlf_pl : mlf_per_lane();
+  // items per k_mlf lane, or two lanes per item (k_mlf2): bls/knobs.hpp mlf_per_lane
+  const bls::Knobs& kn = bls::knobs();
+  const uint32_t per_lane = b.mlf_pl ? b.mlf_pl : bls::mlf_per_lane(kn, bls_sets_in_flight());
   if (per_lane == MLF_PAIR) {
-    static const int w2 = [] {
-      const char* e = getenv("BLS_MLF2_WAVES");
-      return e && atoi(e) == 1 ? 1 : 2;
-    }();
-    if (w2 == 2) k_mlf2<2><<<bls_grid_for(2 * count), BLS_BLOCK, 0, s>>>(b, first, count, up, lines, stride, items);
+    if (kn.mlf2_waves == 2) k_mlf2<2><<<bls_grid_for(2 * count), BLS_BLOCK, 0, s>>>(b, first, count, up, lines, stride, items);
     else k_mlf2<1><<<bls_grid_for(2 * count), BLS_BLOCK, 0, s>>>(b, first, count, up, lines, stride, items);
     return hipGetLastError();
   }
@@ -401,55 +387,4 @@ hipError_t launch_k_mlqf_msm(const PipeBufs& b, const MsmBufs& m, uint32_t group
   k_mlf_msm<1><<<MSM_BUCKET_BLOCKS + bls_grid_for(lanes), BLS_BLOCK, 0, s>>>(b, m, count, n, groups, lines, stride,
                                                                             per_lane);
   return hipGetLastError();
-}
-
-uint32_t mlf_per_lane_fixed() {
-  static const uint32_t fixed = [] {
-    const char* e = getenv("BLS_MLF_PER_LANE");
-    const int v = e ? atoi(e) : 0;
-    return (v == 1 || v == 2 || v == 4 || v == (int)MLF_PAIR) ? (uint32_t)v : 0u;
-  }();
-  return fixed;
-}
-
-uint64_t mlf_pair_max() {
-  static const uint64_t pair_max = [] {
-    const char* e = getenv("BLS_MLF_PAIR_MAX");
-    return e ? (uint64_t)strtoull(e, nullptr, 10) : 16384ull;
-  }();
-  return pair_max;
-}
-
-// Items per k_mlf lane for the launches after the first pass (a failed merged check's
-// chunk signature sums, the individually verified requests' own loops and sums): their
-// items never share f, so more than one per lane only lengthens the chain that the failing
-// call waits on (4 per lane ran each such launch for the whole 14 ms of a plateau pass's f
-// side, profiles/r05_cfg5_fallback.json).  Two lanes per item up to $BLS_MLF_PAIR_MAX
-// items, else one; $BLS_MLF_PER_LANE still fixes it; $BLS_MLF_ALONE=0 returns 0 (the
-// launches keep the first pass's shape, as before round 5's change).
-uint32_t mlf_per_lane_alone(uint32_t count) {
-  static const bool off = [] {
-    const char* e = getenv("BLS_MLF_ALONE");
-    return e && atoi(e) == 0;
-  }();
-  if (off) return 0u;
-  const uint32_t fixed = mlf_per_lane_fixed();
-  if (fixed) return fixed;
-  return count <= mlf_pair_max() ? MLF_PAIR : 1u;
-}
-
-uint32_t mlf_per_lane() {
-  const uint32_t fixed = mlf_per_lane_fixed();
-  const uint64_t pair_max = mlf_pair_max();
-  static const uint64_t pl2_min = [] {
-    const char* e = getenv("BLS_MLF_PL2_MIN");
-    return e ? (uint64_t)strtoull(e, nullptr, 10) : 98304ull;
-  }();
-  static const uint64_t pl4_min = [] {
-    const char* e = getenv("BLS_MLF_PL4_MIN");
-    return e ? (uint64_t)strtoull(e, nullptr, 10) : 200000ull;
-  }();
-  if (fixed) return fixed;
-  const uint64_t k = bls_sets_in_flight();
-  return k > pl4_min ? 4u : (k > pl2_min ? 2u : (k > pair_max ? 1u : MLF_PAIR));
 }

@@ -24,6 +24,7 @@
 // status + chunks) only when the count is non-zero.
 #define BLS_FP_D28 1  // 28-bit-digit Montgomery product (bls/field.hpp)
 #include "../launchers.hpp"
+#include "../bls/knobs.hpp"
 
 using namespace bls;
 
@@ -281,34 +282,6 @@ __global__ __launch_bounds__(COOP_LANES) void k_mln_items(PipeBufs b, const Coop
   mln_items<1>(b, *envp, sh.frame, &sh.flag, (int)(sizeof(sh.frame) / sizeof(Fp)), i, i + 1, 0u);
 }
 
-// Sets per wavefront for a batch: 1 for small batches (latency: one set per two
-// wavefronts spreads a small call over more SIMDs); from BLS_PACK_MIN_SETS sets on, 2
-// while the process has at most $BLS_PACK3_INFLIGHT (2,048) sets in flight, else 3
-// (three sets' steps share one wavefront's lanes: on the round-5 interpreter 1024-set
-// calls at 4 x 1 / 8 x 1 / 12 x 1 contexts run 0.58M / 0.70M / 0.79M sets/s packed 3
-// against 0.49-0.53M / 0.63-0.66M / 0.68-0.70M packed 2 and ~0.26M unpacked, but at
-// 2 x 1 0.32M against 0.35M; profiles/r05_ab_perset_pack.json; round 4 had 2 ahead of 3
-// everywhere).  $BLS_PACK (1, 2 or 3) forces a packing; $BLS_PACK_MIN overrides the
-// threshold.
-#define BLS_PACK_MIN_SETS 512u
-static uint32_t pack_for(uint32_t n_sets) {
-  static const int forced = [] {
-    const char* e = getenv("BLS_PACK");
-    return e ? atoi(e) : 0;
-  }();
-  static const uint32_t min_sets = [] {
-    const char* e = getenv("BLS_PACK_MIN");
-    return e ? (uint32_t)strtoul(e, nullptr, 10) : BLS_PACK_MIN_SETS;
-  }();
-  if (forced >= 1 && forced <= 3) return (uint32_t)forced;
-  static const uint64_t pack3_inflight = [] {
-    const char* e = getenv("BLS_PACK3_INFLIGHT");
-    return e ? (uint64_t)strtoull(e, nullptr, 10) : 2048ull;
-  }();
-  if (n_sets < min_sets) return 1u;
-  return bls_sets_in_flight() > pack3_inflight ? 3u : 2u;
-}
-
 // The aggregated path's Miller loops are the SIMT pair k_mlq / k_mlf
 // (kernels/k_mlq.hip); a test that forces a cooperative packing (BLS_DEBUG_PACK(1 / 2))
 // runs them as the cooperative single-pair loops above instead, 1 or 2 per wavefront.
@@ -341,25 +314,19 @@ hipError_t launch_k_mln(const PipeBufs& b, const CoopEnv& env, uint32_t first, u
 // k_mlq + k_mlf2 takes ~7 ms (2.6 + 4.6; profiles/r05_cfg5_fallback.json "step3"), and the
 // items are few.  Up to $BLS_COOP_ML_MAX items (default 8192; 0 turns it off); 0 items
 // or no ml1_1 program: hipErrorNotSupported (the caller takes the SIMT pair).
-uint32_t coop_ml_max() {
-  static const uint32_t v = [] {
-    const char* e = getenv("BLS_COOP_ML_MAX");
-    return e ? (uint32_t)strtoul(e, nullptr, 10) : 8192u;
-  }();
-  return v;
-}
-
 hipError_t launch_k_mln_coop(const PipeBufs& b, const CoopEnv& env, uint32_t first, uint32_t count,
                              const uint32_t* items, hipStream_t s) {
   if (count == 0) return hipSuccess;
-  if (env.ml1_1.n == 0 || count > coop_ml_max()) return hipErrorNotSupported;
+  if (env.ml1_1.n == 0 || count > bls::knobs().coop_ml_max) return hipErrorNotSupported;
   if (items) k_mln_items<CoopLds><<<count, COOP_LANES, 0, s>>>(b, env.dev, items);
   else k_mln<1, CoopLds><<<count, COOP_LANES, 0, s>>>(b, env.dev, first, count, 0u);
   return hipGetLastError();
 }
 
 hipError_t launch_k_pset(const PipeBufs& b, const CoopEnv& env, hipStream_t s) {
-  const uint32_t S = (b.pack >= 1 && b.pack <= 3) ? b.pack : pack_for(b.n_sets);
+  // sets per wavefront: a test's BLS_DEBUG_PACK, else bls/knobs.hpp pack_for
+  const uint32_t S =
+      (b.pack >= 1 && b.pack <= 3) ? b.pack : bls::pack_for(bls::knobs(), b.n_sets, bls_sets_in_flight());
   if (S == 3 && env.packed[1].ml2.n > 0) {
     k_psetn<3, COOP_FRAME3><<<(b.n_sets + 2) / 3, COOP_LANES, 0, s>>>(b, env.dev);
   } else if (S == 2 && env.packed[0].ml2.n > 0) {

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include "bls/pipeline.hpp"
+#include "bls/plan_shape.hpp"
 
 #define BLS_BLOCK 64
 
@@ -18,7 +19,6 @@ static inline unsigned bls_grid_for(uint32_t n) { return (n + BLS_BLOCK - 1) / B
 
 hipError_t launch_k_pk(const bls::PipeBufs& b, hipStream_t s);
 hipError_t launch_k_pk_agg(const bls::PipeBufs& b, hipStream_t s);
-#define BLS_AGG_WAVE_MIN 16u  // aggregate sets of at least this many keys: k_pk_agg
 hipError_t launch_k_aggregate(const bls::PipeBufs& b, uint8_t* out96, hipStream_t s);
 hipError_t launch_k_load_pubkeys(const uint8_t* pks, uint32_t n, uint32_t pk_len, bls::G1A* out, int32_t* codes,
                                  hipStream_t s);
@@ -45,10 +45,6 @@ size_t msm_seg_cap(uint32_t n_sets);
 // bucket counts, then the tickets: k_msm_bin's, the windows', one per window's bucket blocks
 #define MSM_STATE_WORDS (MSM_BUCKETS + 6u)
 static_assert(MSM_BUCKETS == bls::MSM_NB && MSM_STATE_WORDS == bls::MSM_NB + bls::MSM_TICKETS, "bls/msm_bufs.hpp");
-// k_msm_bin: 22-bit bucket slots, <= 2 entries per set and bucket
-#define MSM_MAX_SETS (1u << 21)
-// mlf_per_lane(): one item per TWO f lanes (kernels/k_mlq.hip k_mlf2)
-#define MLF_PAIR 3u
 // the merged signature sum into the chunk groups' virtual sets vbase .. vbase + groups:
 // the serial form, five launches
 hipError_t launch_k_msm(const bls::PipeBufs& b, const MsmBufs& m, uint32_t groups, uint32_t vbase, hipStream_t s);
@@ -102,7 +98,6 @@ hipError_t launch_k_fold(const bls::PipeBufs& b, const bls::CoopEnv& env, const 
                          uint32_t step, hipStream_t s);
 // SIMT final exponentiations, one lane per chunk / request (kernels/k_fin_simt.hip), for
 // a failing pass's many tasks: save = 4 Fp12 of device memory per task
-uint32_t fe_simt_min();
 hipError_t launch_k_chunk_simt(const bls::PipeBufs& b, bls::Fp12* save, hipStream_t s);
 hipError_t launch_k_indiv_simt(const bls::PipeBufs& b, const bls::GroupBufs& g, bls::Fp12* save, hipStream_t s);
 hipError_t launch_k_coop_probe(const bls::CoopEnv& env, bls::CoopProg pg, uint32_t blocks, uint32_t reps,
@@ -124,18 +119,11 @@ bool k_mln_list_ok(const bls::PipeBufs& b);
 hipError_t launch_k_mln_list(const bls::PipeBufs& b, const uint32_t* items, uint32_t count, hipStream_t s);
 // cooperative single-pair loops of [first, first + count) or of items[0, count), one
 // wavefront each, for a failing pass's later launches; hipErrorNotSupported above
-// coop_ml_max() items (kernels/k_pset.hip)
+// $BLS_COOP_ML_MAX items (kernels/k_pset.hip)
 hipError_t launch_k_mln_coop(const bls::PipeBufs& b, const bls::CoopEnv& env, uint32_t first, uint32_t count,
                              const uint32_t* items, hipStream_t s);
-uint32_t coop_ml_max();
 size_t mlq_line_words(uint32_t count);
 // sets in the verify calls currently running in this process (every context)
 uint64_t bls_sets_in_flight();
-// items per lane of k_mlf (1, 2 or 4) for a launch now (kernels/k_mlq.hip)
-uint32_t mlf_per_lane();
-// ... and for a launch after the first pass (items that never share f), by its item count
-uint32_t mlf_per_lane_alone(uint32_t count);
-uint32_t mlf_per_lane_fixed();
-uint64_t mlf_pair_max();
 hipError_t launch_k_mlqf(const bls::PipeBufs& b, uint32_t first, uint32_t count, bool own_only, uint32_t* lines,
                          hipStream_t s, const uint32_t* items = nullptr);

@@ -6,12 +6,15 @@
 // -fsanitize=address,undefined: an index past a plan's vectors or the caller's arrays is a
 // report there.  The program re-checks the invariants the device relies on (segments
 // inside their group and level, every set in exactly one unit, runs inside the requests);
-// the value checks against a Python restatement are tests/test_plan_cpu.py's.
+// the value checks against a Python restatement are tests/test_plan_cpu.py's.  It also
+// parses every knob (bls/knobs.hpp) and runs plan_pass, the decision table of a whole
+// pass, over the shapes of tests/test_knobs_cpu.py (which checks their values).
 //
 //   plan_host            prints "ok <checks>" and exits 0, or the first mismatch and 1
 #include <stdio.h>
 #include <string.h>
 
+#include <string>
 #include <vector>
 
 #include "plan_exports.hpp"
@@ -212,7 +215,87 @@ static int check_batch_cases() {
   return 0;
 }
 
+// every knob parsed from an environment that sets it (to `value`) and from one that does
+// not; the table's names are distinct
+static int knobs_cases() {
+  char table[1 << 14];
+  CHECK(hs_knob_table(table, sizeof(table)) > 0, "knob table does not fit");
+  std::vector<std::string> names;
+  for (const char* p = table; *p; p = strchr(p, '\n') + 1) names.emplace_back(p, strchr(p, '\t') - p);
+  for (size_t a = 0; a < names.size(); ++a)
+    for (size_t b = 0; b < a; ++b) CHECK(names[a] != names[b], "knob %s twice", names[a].c_str());
+  U32s out(4 * names.size() + 8);
+  for (const char* value : {"", "0", "1", "3", "-1", "poll", "18446744073709551615"}) {
+    std::string all;
+    for (const std::string& nm : names) {
+      const std::string one = nm + "=" + value + "\n";
+      CHECK(hs_knobs_parse(one.c_str(), out.data(), (uint32_t)out.size()) == (int)(1 + 2 * names.size()), "%s", nm.c_str());
+      all += one;
+    }
+    CHECK(hs_knobs_parse(all.c_str(), out.data(), (uint32_t)out.size()) > 0, "all knobs = %s", value);
+    for (int which = 0; which < 8; ++which)
+      for (unsigned long long in_flight : {0ull, 60001ull, ~0ull}) (void)hs_knob_decide(all.c_str(), which, 0, 2049, in_flight);
+  }
+  CHECK(hs_knobs_parse("", out.data(), (uint32_t)out.size()) > 0 && hs_knobs_parse(nullptr, out.data(), (uint32_t)out.size()) > 0,
+        "no environment");
+  return 0;
+}
+
+// plan_pass over one batch: the layout the carve and the kernels rely on
+static int pass_case(const char* env, const U32s& req_sizes, const std::vector<uint8_t>& batchable, const U32s& roots,
+                     int ask, const U32s& aux, uint32_t flags, int failed, unsigned long long in_flight) {
+  const U32s req_off = offsets(req_sizes);
+  const uint32_t R = (uint32_t)req_sizes.size(), n = req_off.back();
+  U32s out(256 + R);
+  const int w = hs_plan_pass(env, req_off.data(), R, batchable.data(), roots.data(), ask, aux.empty() ? nullptr : aux.data(),
+                             aux.empty() ? 0u : (uint32_t)aux.size() - 1, flags, failed, in_flight, out.data(),
+                             (uint32_t)out.size());
+  CHECK(w > 0, "plan_pass output does not fit");
+  const std::vector<U32s> v = parse(out, w);
+  const U32s &sh = v[0], &sizes = v[1], &chunk_off = v[2];
+  const uint32_t C = (uint32_t)chunk_off.size() - 1;
+  const uint32_t sigagg = sh[12], n_units = sh[19], unit_base = sh[20], indiv_vbase = sh[21], n_total = sh[22];
+  CHECK(sh[0] == n && sh[1] == R && sh[2] == C, "n, R, C");
+  CHECK(unit_base == n + C && indiv_vbase == unit_base + n_units, "unit_base %u indiv_vbase %u", unit_base, indiv_vbase);
+  CHECK(n_total == (sigagg ? indiv_vbase + R : n) && sh[23] == (sigagg ? indiv_vbase : n), "n_total %u", n_total);
+  CHECK(sh[11] == (sh[9] && !sh[10]), "merged = eligible and not skipped");
+  CHECK(sh[17] <= sh[16] && sh[16] <= sh[15] && sh[15] <= sh[11] && sh[15] <= sigagg, "msm_overlap <= use_msm <= use_total");
+  CHECK(sizes[0] <= n && sizes[1] <= n && sizes[2] <= n, "a sum plan over more than the sets");
+  CHECK(sizes[4] == (sh[18] ? unit_base + n_units : 0u), "ml_dom of %u items", sizes[4]);
+  return 0;
+}
+
+static int pass_cases() {
+  U32s ones(64, 1), distinct(64), shared(64), none;
+  for (uint32_t i = 0; i < 64; ++i) distinct[i] = i, shared[i] = i / 8;
+  const std::vector<uint8_t> all(70, 1);
+  std::vector<uint8_t> some(all);
+  some[30] = 0;
+  const uint32_t on = BLS_DEBUG_SIGAGG_ON, off = BLS_DEBUG_SIGAGG_OFF;
+  for (uint32_t flags : {on, off, on | BLS_DEBUG_MSM, on | BLS_DEBUG_MSM | BLS_DEBUG_MSM_SERIAL, on | BLS_DEBUG_NO_UNITS,
+                         on | BLS_DEBUG_MERGED_EVERY_PASS, on | BLS_DEBUG_NO_MSG_DEDUP, 0u})
+    for (int failed = 0; failed < 2; ++failed)
+      for (unsigned long long in_flight : {0ull, 60001ull}) {
+        for (int ask = 0; ask < 3; ++ask)
+          if (pass_case("", ones, all, ask ? distinct : shared, ask, none, flags, failed, in_flight)) return 1;
+        if (pass_case("BLS_MERGED_AFTER_FAIL=1\n", ones, some, shared, 0, none, flags, failed, in_flight)) return 1;
+        if (pass_case("", ones, all, distinct, 0, {0, 40, 64}, flags, failed, in_flight)) return 1;
+        if (pass_case("", ones, all, shared, 3, {0, 20, 64}, flags, failed, in_flight)) return 1;
+        if (pass_case("", ones, all, shared, 3, {0, 20, 21, 64}, flags, failed, in_flight)) return 1;
+      }
+  // 16 requests (one chunk), 3 and 4 (group tests), requests of 0 .. 5 sets, no set at all
+  for (uint32_t R : {16u, 3u, 4u}) if (pass_case("", U32s(R, 1), all, distinct, 0, none, on, 0, 0)) return 1;
+  U32s mixed(70), roots;
+  for (uint32_t r = 0; r < 70; ++r) mixed[r] = (7 * r) % 6;
+  for (uint32_t i = 0; i < offsets(mixed).back(); ++i) roots.push_back(i / 6);
+  for (uint32_t flags : {on, off})
+    if (pass_case("", mixed, all, roots, 0, none, flags, 0, 1000000) || pass_case("", mixed, some, roots, 1, none, flags, 1, 0)) return 1;
+  if (pass_case("", {0, 0}, all, none, 0, none, on, 0, 60001)) return 1;
+  return 0;
+}
+
 int main() {
+  if (knobs_cases() || pass_cases()) return 1;
   const U32s sizes = {0, 1, 4, 5, 16, 17, 65};
   if (gsum_case(sizes) || gsum_case({65, 17, 16, 5, 4, 1, 0}) || gsum_case({0, 65, 0}) || gsum_case({0})) return 1;
   // two chunks of 16 one-set requests, roots shared 8-way inside a chunk and across both
