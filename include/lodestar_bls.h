@@ -348,6 +348,63 @@ int bls_gpu_final_check(bls_gpu_ctx* ctx, const uint8_t* partials576, uint32_t n
 int bls_gpu_aggregate_pubkeys(bls_gpu_ctx* ctx, const uint32_t* set_pk_offsets, const uint32_t* pk_indices,
                               uint32_t n_sets, uint8_t* out96, int32_t* codes);
 
+/* Committee groups: aggregate sets as they arrive on the wire, a committee plus a bitfield
+ * (Attestation.aggregation_bits over a beacon committee, SyncAggregate.sync_committee_bits
+ * over the sync committee), instead of the index list the host would expand them into.  The
+ * committees are fixed for an epoch or a sync-committee period, so their member lists are
+ * registered once and kept on the device with each committee's total key: a set whose field
+ * has c of n bits set costs min(c, n - c + 1) point additions, not c, and its call ships
+ * n / 8 bytes, not 4 c.
+ *
+ * A group is what the host holds as one unit -- one epoch's shuffling, or one sync
+ * committee -- and is registered and replaced wholesale.  Groups belong to the context
+ * (each context of a device registers them for itself; holding them beside the shared key
+ * table of bls_gpu_share_pubkeys is a follow-up). */
+#define BLS_COMMITTEE_GROUPS 8u               /* previous/current/next shuffling, current/next sync committee, spare */
+#define BLS_COMMITTEE_MAX_MEMBERS 131072u     /* per committee */
+#define BLS_SET_NO_COMMITTEE 0xFFFFFFFFu
+#define BLS_COMMITTEE_REF(group, index) (((uint32_t)(group) << 24) | (uint32_t)(index))  /* index < 2^24 */
+
+/* Replace group `group` (0..7) by n committees; committee c = table indices
+ * members[member_offsets[c] .. member_offsets[c+1]), in committee order, duplicates allowed
+ * (sync committees repeat validators).  n == 0 drops the group.  The call copies both arrays
+ * to the device and sums every committee's members there (with multiplicity); the key
+ * table is append-only, so the totals stay valid after later bls_gpu_load_pubkeys calls.
+ * It holds the context's lock: no call of the context is in flight while a group changes.
+ * Returns 0; -2 with nothing changed and a bls_gpu_last_error message naming the committee
+ * for group >= BLS_COMMITTEE_GROUPS, member_offsets that do not run monotonically from 0, an
+ * empty committee, one of more than BLS_COMMITTEE_MAX_MEMBERS members, or a member at or past
+ * the table's size; -1 (nothing changed either) for a device failure. */
+int bls_gpu_set_committee_group(bls_gpu_ctx* ctx, uint32_t group, uint32_t n,
+                                const uint32_t* member_offsets, const uint32_t* members);
+typedef struct bls_committee_info { uint32_t n_committees; uint32_t n_members; uint64_t device_bytes; } bls_committee_info;
+/* What group `group` holds (all zero: not registered); -2 for group >= BLS_COMMITTEE_GROUPS. */
+int bls_gpu_committee_group_info(bls_gpu_ctx* ctx, uint32_t group, bls_committee_info* out);
+
+typedef struct bls_committee_sets {
+  const uint32_t* set_committee;  /* n_sets: BLS_COMMITTEE_REF(group, index), or BLS_SET_NO_COMMITTEE:
+                                     the set uses batch->set_pk_offsets / pk_indices as before */
+  const uint32_t* set_bits_off;   /* n_sets + 1 byte offsets into bits (equal for a NO_COMMITTEE set) */
+  const uint8_t* bits;            /* member j of the committee = bit (j & 7) of byte j >> 3 (SSZ order),
+                                     without a Bitlist delimiter bit */
+} bls_committee_sets;
+
+/* bls_gpu_verify for a batch some of whose sets name a committee.  A committee set is
+ * exactly the aggregate set whose index list is the committee's members at the set bits, in
+ * order: the same verdicts and bls_stats counters as bls_gpu_verify on the expanded lists.
+ * Its status follows the index-list path: no bit set BLS_CODE_EMPTY_AGGREGATE; an
+ * unregistered group, an index past the group, a byte count other than ceil(members / 8) or
+ * a set bit at or past the member count BLS_CODE_BAD_ENCODING.  The batch must be in table
+ * mode (set_pk_offsets != NULL) and a committee set's own index list empty; the call may mix
+ * both kinds of set.  -2 otherwise, and for set_bits_off that does not run monotonically
+ * from 0 or a NO_COMMITTEE set that carries bits. */
+int bls_gpu_verify_committees(bls_gpu_ctx* ctx, const bls_batch* batch, const bls_committee_sets* cs,
+                              int32_t* verdicts, bls_stats* stats);
+/* bls_gpu_aggregate_pubkeys for n_sets committee sets (every set names a committee): the
+ * same bytes and codes as the expanded index lists give. */
+int bls_gpu_aggregate_committee_bits(bls_gpu_ctx* ctx, const bls_committee_sets* cs, uint32_t n_sets,
+                                     uint8_t* out96, int32_t* codes);
+
 /* G2 signature aggregation for the op pools:
  * Signature.aggregate(sigs.map((s) => Signature.fromBytes(s, undefined, true))) for each
  * of n_lists lists (aggregatedAttestationPool.ts:320-327 aggregateInto,

@@ -122,15 +122,23 @@ function packRequests(jobs, seed) {
   let nSets = 0;
   let nIdx = 0;
   let raw = false;
+  let nBits = -1; // bytes of committee bits; -1: no committee set in the call
   for (let r = 0; r < nReq; r++) {
     const ss = jobs[r].sets;
     nSets += ss.length;
     for (let i = 0; i < ss.length; i++) {
       const s = ss[i];
-      if (s.pubkey !== undefined) raw = true;
+      if (s.type === "committee") nBits = (nBits < 0 ? 0 : nBits) + s.bits.length;
+      else if (s.pubkey !== undefined) raw = true;
       else nIdx += s.pubkeyIndices.length;
     }
   }
+  if (raw && nBits >= 0) throw Error("mixed raw pubkeys / committee sets in one call");
+  // committee sets (bls_committee_sets): the call then goes to addon.verifyCommittees
+  const setCommittee = nBits >= 0 ? new Uint32Array(nSets).fill(SET_NO_COMMITTEE) : null;
+  const setBitsOff = nBits >= 0 ? new Uint32Array(nSets + 1) : null;
+  const bits = nBits >= 0 ? Buffer.allocUnsafe(Math.max(nBits, 1)) : null;
+  let qb = 0;
   const reqSetOffsets = new Uint32Array(nReq + 1);
   const reqBatchable = new Uint8Array(Math.max(nReq, 1));
   const messages = Buffer.allocUnsafe(Math.max(32 * nSets, 1));
@@ -162,17 +170,63 @@ function packRequests(jobs, seed) {
         if (s.pubkey === undefined) throw Error("mixed raw / table pubkeys in one call");
         if (s.pubkey.length !== 96) throw Error("raw pubkeys are 96 bytes (uncompressed affine)");
         pubkeys.set(s.pubkey, 96 * k);
+      } else if (s.type === "committee") {
+        setCommittee[k] = committeeRef(s.group, s.index);
+        bits.set(s.bits, qb);
+        qb += s.bits.length;
+        setPkOffsets[k + 1] = q;
       } else {
         const ix = s.pubkeyIndices;
         for (let t = 0; t < ix.length; t++) pkIndices[q++] = ix[t];
         setPkOffsets[k + 1] = q;
       }
+      if (setBitsOff !== null) setBitsOff[k + 1] = qb;
       k++;
     }
     reqSetOffsets[r + 1] = k;
   }
   return {reqSetOffsets, reqBatchable, messages, signatures, signatureLens: lens, pubkeys, setPkOffsets, pkIndices,
-          seed: seed || null};
+          setCommittee, setBitsOff, bits, seed: seed || null};
+}
+
+/** the request of addon.verifySync (bls_gpu_verify): committee sets go through verifySignatureSets */
+function packSync(jobs) {
+  const req = packRequests(jobs);
+  if (req.setCommittee !== null) throw Error("committee sets are verified through verifySignatureSets");
+  return req;
+}
+
+/** BLS_COMMITTEE_REF / BLS_SET_NO_COMMITTEE (include/lodestar_bls.h) */
+const SET_NO_COMMITTEE = 0xffffffff;
+const COMMITTEE_GROUPS = 8;
+function committeeRef(group, index) {
+  if (!(group >= 0 && group < 256 && index >= 0 && index < 1 << 24)) throw Error("committee reference out of range");
+  return ((group << 24) | index) >>> 0;
+}
+
+function popcountBytes(bits) {
+  let c = 0;
+  for (let i = 0; i < bits.length; i++) {
+    let b = bits[i];
+    b = b - ((b >> 1) & 0x55);
+    b = (b & 0x33) + ((b >> 2) & 0x33);
+    c += (b + (b >> 4)) & 0x0f;
+  }
+  return c;
+}
+
+/** Pack member lists into the arrays of addon.setCommitteeGroup (bls_gpu_set_committee_group) */
+function packCommittees(committees) {
+  let n = 0;
+  for (const c of committees) n += c.length;
+  const memberOffsets = new Uint32Array(committees.length > 0 ? committees.length + 1 : 0);
+  const members = new Uint32Array(Math.max(n, 1));
+  let q = 0;
+  committees.forEach((c, k) => {
+    for (let t = 0; t < c.length; t++) members[q++] = c[t];
+    memberOffsets[k + 1] = q;
+  });
+  return {memberOffsets, members};
 }
 
 /** Pack same-message jobs ({message, indices, signatures}) into the SoA request of
@@ -255,7 +309,16 @@ function shardBounds(n, parts) {
 
 /** Routing weight of a set: 1, or 1 + k / 1024 for an aggregate of k table keys (a G1
  * addition is ~11 of a set's ~12.7k Fp products; lodestar_amd/verifier.py set_weight). */
-function setWeight(s) {
+function setWeight(s, groups) {
+  if (s.type === "committee") {
+    // 1 + min(c, n - c) keys in place of k: the set bits summed directly, or the clear ones
+    // taken from the committee's total (bls/committee.hpp committee_weight)
+    const c = popcountBytes(s.bits);
+    const g = groups !== undefined ? groups.get(s.group) : undefined;
+    const n = g !== undefined && g[s.index] !== undefined ? g[s.index].length : c;
+    const k = 1 + Math.min(c, Math.max(n - c, 0));
+    return k > 1 ? 1 + k / AGG_KEY_WEIGHT : 1;
+  }
   const ix = s.pubkeyIndices;
   return ix !== undefined && ix.length > 1 ? 1 + ix.length / AGG_KEY_WEIGHT : 1;
 }
@@ -278,10 +341,27 @@ const SSZ_KINDS = {
 function getAggregatedPubkeysCount(sets) {
   let n = 0;
   for (const s of sets) {
+    if (s.type === "committee") {
+      n += popcountBytes(s.bits);
+      continue;
+    }
     const agg = s.type !== undefined ? s.type === "aggregate" : s.pubkeyIndices !== undefined && s.pubkeyIndices.length > 1;
     if (agg && s.pubkeyIndices !== undefined) n += s.pubkeyIndices.length;
   }
   return n;
+}
+
+/** The message a job goes out in: raw keys (the reference's worker message), table indices
+ * (bls_gpu_verify), or a job holding a committee set (bls_gpu_verify_committees: its own
+ * message, which may carry index-list sets beside the committee sets) */
+const KIND_TABLE = 0;
+const KIND_RAW = 1;
+const KIND_COMMITTEE = 2;
+function jobKind(j) {
+  const ss = j.sets;
+  if (ss.length > 0 && ss[0].pubkey !== undefined) return KIND_RAW;
+  for (let i = 0; i < ss.length; i++) if (ss[i].type === "committee") return KIND_COMMITTEE;
+  return KIND_TABLE;
 }
 
 /** A queued job: its BlsWorkReq ({batchable, sets}) and its promise's handlers. */
@@ -362,6 +442,7 @@ class GpuBlsVerifier {
       warn(`GpuBlsVerifier: the libuv pool has ${uvSize} threads < contexts + 2 = ${this.ctxs.length + 2}; ` +
         "GPU calls will queue for libuv threads (set UV_THREADPOOL_SIZE in the environment before starting node)");
     }
+    this.groups = new Map(); // committee groups as registered (setCommitteeGroup): group -> member lists
     this.jobs = []; // queue: jobs[jobsHead..] are pending
     this.jobsHead = 0;
     this.smJobs = []; // same-message jobs ({message, indices, signatures, resolve, reject}), their own kind
@@ -404,6 +485,47 @@ class GpuBlsVerifier {
     });
   }
 
+  /** Register (replace; an empty list drops) committee group `group` (0..7) on every context
+   * of every device: `committees` is a list of member lists of validator indices (one
+   * epoch's shuffling, or one sync committee).  Sets {type: "committee", group, index, bits,
+   * signingRoot, signature} then verify as the aggregate of committee `index`'s members at
+   * the set bits (SSZ order).  Groups belong to a context (bls_gpu_set_committee_group), so
+   * each context gets its copy, one after another; the first context's validation decides
+   * for all, so a rejected registration changes none. */
+  async setCommitteeGroup(group, committees) {
+    const lists = committees.map((c) => Array.from(c));
+    const packed = packCommittees(lists);
+    const all = [this.mainCtx].concat(this.ctxs);
+    for (let i = 0; i < all.length; i++) {
+      try {
+        await this.addon.setCommitteeGroup(all[i].handle, group, packed);
+      } catch (e) {
+        throw i === 0 ? e : Error(`committee groups diverged across contexts: ${e.message}`);
+      }
+    }
+    if (lists.length > 0) this.groups.set(group, lists);
+    else this.groups.delete(group);
+  }
+
+  /** Open one more pool context on device slot `slot`: it shares the device's key table and
+   * holds every registered committee group before it takes work. */
+  async addContext(slot = 0) {
+    const addon = this.addon;
+    const c = {handle: addon.init(this.devices[slot], false), inflight: 1, id: this.ctxs.length, slot};
+    if (this.tableCtxs !== null) {
+      const owner = [this.mainCtx].concat(this.ctxs).find((o) => this.devices[o.slot] === this.devices[slot]);
+      addon.sharePubkeys(c.handle, owner.handle);
+    }
+    for (const [group, lists] of Array.from(this.groups.entries()).sort((a, b) => a[0] - b[0])) {
+      await addon.setCommitteeGroup(c.handle, group, packCommittees(lists));
+    }
+    c.inflight = 0;
+    this.ctxs.push(c);
+    this.slotCtxs[slot].push(c);
+    this._scheduleRun();
+    return c;
+  }
+
   /** IBlsVerifier.verifySignatureSets (index.ts:134-174).  Returns a Promise<boolean>. */
   verifySignatureSets(sets, opts) {
     const o = opts || NO_OPTS;
@@ -427,7 +549,9 @@ class GpuBlsVerifier {
     // one job (chunkifyMaximizeChunkSize gives one chunk): the job resolves to the
     // boolean verdict, so it is the call's result
     if (n > 0 && n <= MAX_SIGNATURE_SETS_PER_JOB) return this._queue(batchable, sets);
-    if (!batchable && n >= this.splitCallMinSets && this.nSlots > 1 && this.slotCtxs.every((c) => c.length > 0)) {
+    // (a sharded call keeps index lists, as bls_gpu_partial does)
+    if (!batchable && n >= this.splitCallMinSets && this.nSlots > 1 && this.slotCtxs.every((c) => c.length > 0) &&
+        !sets.some((s) => s.type === "committee")) {
       return this._splitCall(sets);
     }
     return this._queueCall(sets, batchable);
@@ -587,7 +711,7 @@ class GpuBlsVerifier {
    * signature does not decode (Signature.fromBytes(sig, undefined, true)).
    */
   verifySignatureSetSync(set) {
-    return this._settle(this.addon.verifySync(this.mainCtx.handle, packRequests([{batchable: false, sets: [set]}])), 0);
+    return this._settle(this.addon.verifySync(this.mainCtx.handle, packSync([{batchable: false, sets: [set]}])), 0);
   }
 
   /** verifySignatureSet over many sets in one GPU call (e.g. every inline check of a
@@ -596,7 +720,7 @@ class GpuBlsVerifier {
    * signature does not decode, so a truthiness check of `valid` can never pass it; one
    * bad set does not hide the other sets' verdicts (lodestar_amd/stf.py likewise). */
   verifySignatureSetsEachSync(sets) {
-    const v = this.addon.verifySync(this.mainCtx.handle, packRequests(sets.map((s) => ({batchable: false, sets: [s]}))));
+    const v = this.addon.verifySync(this.mainCtx.handle, packSync(sets.map((s) => ({batchable: false, sets: [s]}))));
     return sets.map((_, i) => {
       try {
         return {valid: this._settle(v, i)};
@@ -650,7 +774,10 @@ class GpuBlsVerifier {
 
   async _call(ctx, jobs) {
     if (this.closed && this.ctxs.length === 0) throw Error("QUEUE_ABORTED");
-    return this._run(ctx, () => this.addon.verify(ctx.handle, packRequests(jobs)));
+    const req = packRequests(jobs);
+    // a call holding a committee set is its own kind of message (bls_gpu_verify_committees)
+    if (req.setCommittee !== null) return this._run(ctx, () => this.addon.verifyCommittees(ctx.handle, req));
+    return this._run(ctx, () => this.addon.verify(ctx.handle, req));
   }
 
   /** run fn (an addon call returning a promise) with the context counted in flight */
@@ -903,21 +1030,20 @@ class GpuBlsVerifier {
   _startJobs(ctx) {
     const q = this.jobs;
     const first = q[this.jobsHead];
-    const kind = first.sets[0] !== undefined && first.sets[0].pubkey !== undefined;
+    const kind = jobKind(first);
     const jobs = [];
     let skipped = null;
     let total = 0;
     let weight = 0;
-    const cap = kind ? MAX_SIGNATURE_SETS_PER_JOB : this.maxSetsPerCall;
+    const cap = kind === KIND_RAW ? MAX_SIGNATURE_SETS_PER_JOB : this.maxSetsPerCall;
     while (this.jobsHead < q.length && total < cap) {
       const j = q[this.jobsHead];
       q[this.jobsHead++] = undefined;
-      const s0 = j.sets[0];
-      if ((s0 !== undefined && s0.pubkey !== undefined) === kind) {
+      if (jobKind(j) === kind) {
         jobs.push(j);
         const ss = j.sets;
         total += ss.length;
-        for (let i = 0; i < ss.length; i++) weight += setWeight(ss[i]);
+        for (let i = 0; i < ss.length; i++) weight += setWeight(ss[i], this.groups);
       } else {
         (skipped || (skipped = [])).push(j); // other pubkey form: a later call
       }
@@ -1008,6 +1134,10 @@ module.exports = {
   DEPOSITS_MAX_CALL,
   shardBounds,
   setWeight,
+  packCommittees,
+  committeeRef,
+  SET_NO_COMMITTEE,
+  COMMITTEE_GROUPS,
   getAggregatedPubkeysCount,
   ERROR_MESSAGES,
   SSZ_KINDS,

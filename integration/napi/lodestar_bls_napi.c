@@ -251,7 +251,8 @@ static napi_value js_pubkeys_info(napi_env env, napi_callback_info info) {
   return obj;
 }
 
-enum { JOB_VERIFY = 0, JOB_PARTIAL = 1, JOB_FINAL = 2, JOB_SAME_MSG = 3, JOB_DEPOSITS = 4 };
+enum { JOB_VERIFY = 0, JOB_PARTIAL = 1, JOB_FINAL = 2, JOB_SAME_MSG = 3, JOB_DEPOSITS = 4, JOB_COMMITTEES = 5,
+       JOB_SET_GROUP = 6 };
 
 typedef struct {
   int kind;
@@ -260,6 +261,9 @@ typedef struct {
   bls_batch batch;
   bls_same_msg_batch same;  /* JOB_SAME_MSG */
   bls_deposit_batch dep;    /* JOB_DEPOSITS */
+  bls_committee_sets cs;    /* JOB_COMMITTEES (with batch) */
+  uint32_t group, n_committees;          /* JOB_SET_GROUP */
+  const uint32_t *member_offsets, *members;
   napi_ref keep;          /* the request object: keeps the input buffers alive */
   napi_ref keep_handle;   /* the handle object: no finalizer while the job is out */
   int32_t* verdicts;
@@ -311,6 +315,10 @@ static void verify_execute(napi_env env, void* data) {
     j->rc = bls_gpu_verify_same_message(j->ctx, &j->same, j->verdicts, &j->stats);
   else if (j->kind == JOB_DEPOSITS)
     j->rc = bls_gpu_verify_deposits(j->ctx, &j->dep, j->verdicts, &j->stats);
+  else if (j->kind == JOB_COMMITTEES)
+    j->rc = bls_gpu_verify_committees(j->ctx, &j->batch, &j->cs, j->verdicts, &j->stats);
+  else if (j->kind == JOB_SET_GROUP)
+    j->rc = bls_gpu_set_committee_group(j->ctx, j->group, j->n_committees, j->member_offsets, j->members);
   else
     j->rc = bls_gpu_verify(j->ctx, &j->batch, j->verdicts, &j->stats);
   j->t_end_ns = mono_ns();
@@ -325,7 +333,9 @@ static void verify_complete(napi_env env, napi_status status, void* data) {
              j->kind == JOB_PARTIAL ? "bls_gpu_partial"
              : j->kind == JOB_FINAL ? "bls_gpu_final_check"
              : j->kind == JOB_SAME_MSG ? "bls_gpu_verify_same_message"
-             : j->kind == JOB_DEPOSITS ? "bls_gpu_verify_deposits" : "bls_gpu_verify",
+             : j->kind == JOB_DEPOSITS ? "bls_gpu_verify_deposits"
+             : j->kind == JOB_COMMITTEES ? "bls_gpu_verify_committees"
+             : j->kind == JOB_SET_GROUP ? "bls_gpu_set_committee_group" : "bls_gpu_verify",
              j->rc, (int)status,
              j->rc ? bls_gpu_last_error(j->ctx) : "cancelled");
     napi_create_string_utf8(env, text, NAPI_AUTO_LENGTH, &msg);
@@ -358,6 +368,10 @@ static void verify_complete(napi_env env, napi_status status, void* data) {
   } else if (j->kind == JOB_FINAL) {
     napi_value out;
     napi_get_boolean(env, j->verdict == 1, &out);
+    napi_resolve_deferred(env, j->deferred, out);
+  } else if (j->kind == JOB_SET_GROUP) {
+    napi_value out;
+    napi_get_undefined(env, &out);
     napi_resolve_deferred(env, j->deferred, out);
   } else {
     napi_value ab, out;
@@ -461,6 +475,111 @@ static napi_value js_verify(napi_env env, napi_callback_info info) {
   j->batch = b;
   j->verdicts = (int32_t*)calloc(b.n_reqs ? b.n_reqs : 1, 4);
   return queue_job(env, h, j, argv[0], argv[1]);
+}
+
+/* verifyCommittees(handle, request) -> Promise<Int32Array>: bls_gpu_verify_committees on a
+ * libuv worker.  The request is verify's (table indices) with setCommittee (Uint32Array,
+ * one BLS_COMMITTEE_REF or BLS_SET_NO_COMMITTEE per set), setBitsOff (Uint32Array, n_sets +
+ * 1) and bits (Uint8Array); the library checks the offsets themselves. */
+static napi_value js_verify_committees(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  bls_handle* h = argc >= 2 ? get_handle(env, argv[0]) : NULL;
+  if (!h) {
+    napi_throw_type_error(env, NULL, "verifyCommittees(handle, request): no live handle (closed?)");
+    return NULL;
+  }
+  bls_batch b;
+  if (parse_request(env, argv[1], &b)) return NULL;
+  void *sc, *sbo, *bits;
+  size_t nsc, nsbo, nbits;
+  if (prop(env, argv[1], "setCommittee", &sc, &nsc) || prop(env, argv[1], "setBitsOff", &sbo, &nsbo) ||
+      prop(env, argv[1], "bits", &bits, &nbits) || !sc || !sbo) {
+    napi_throw_type_error(env, NULL, "verifyCommittees: setCommittee / setBitsOff / bits missing");
+    return NULL;
+  }
+  const size_t ns = b.n_sets;
+  if (nsc < 4 * ns || nsbo < 4 * (ns + 1) || nbits < ((const uint32_t*)sbo)[ns]) {
+    napi_throw_range_error(env, NULL, "verifyCommittees: setCommittee, setBitsOff or bits is shorter than n_sets "
+                                      "and the last offset require");
+    return NULL;
+  }
+  verify_job* j = (verify_job*)calloc(1, sizeof(verify_job));
+  j->kind = JOB_COMMITTEES;
+  j->batch = b;
+  j->cs.set_committee = (const uint32_t*)sc;
+  j->cs.set_bits_off = (const uint32_t*)sbo;
+  j->cs.bits = (const uint8_t*)bits;
+  j->verdicts = (int32_t*)calloc(b.n_reqs ? b.n_reqs : 1, 4);
+  return queue_job(env, h, j, argv[0], argv[1]);
+}
+
+/* setCommitteeGroup(handle, group, {memberOffsets, members}) -> Promise<void>:
+ * bls_gpu_set_committee_group on a libuv worker (an epoch's shuffling is a few MB to copy
+ * and ~2048 committees to sum); n = memberOffsets.length - 1, an empty memberOffsets drops
+ * the group.  A rejected registration rejects with the library's message. */
+static napi_value js_set_committee_group(napi_env env, napi_callback_info info) {
+  size_t argc = 3;
+  napi_value argv[3];
+  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  bls_handle* h = argc >= 3 ? get_handle(env, argv[0]) : NULL;
+  uint32_t group = 0;
+  void *mo, *mem;
+  size_t nmo, nmem;
+  if (!h || napi_get_value_uint32(env, argv[1], &group) != napi_ok || prop(env, argv[2], "memberOffsets", &mo, &nmo) ||
+      prop(env, argv[2], "members", &mem, &nmem)) {
+    napi_throw_type_error(env, NULL, "setCommitteeGroup(handle, group, {memberOffsets, members})");
+    return NULL;
+  }
+  const uint32_t n = nmo >= 8 ? (uint32_t)(nmo / 4 - 1) : 0;
+  /* members must hold what the last offset says when the offsets are monotone; the library
+   * names the committee when they are not */
+  if (n) {
+    const uint32_t* o = (const uint32_t*)mo;
+    uint32_t top = 0;
+    for (uint32_t c = 0; c <= n; ++c)
+      if (o[c] > top) top = o[c];
+    if (nmem < 4 * (size_t)top) {
+      napi_throw_range_error(env, NULL, "setCommitteeGroup: members is shorter than memberOffsets require");
+      return NULL;
+    }
+  }
+  verify_job* j = (verify_job*)calloc(1, sizeof(verify_job));
+  j->kind = JOB_SET_GROUP;
+  j->group = group;
+  j->n_committees = n;
+  j->member_offsets = (const uint32_t*)mo;
+  j->members = (const uint32_t*)mem;
+  return queue_job(env, h, j, argv[0], argv[2]);
+}
+
+/* committeeGroupInfo(handle, group) -> {nCommittees, nMembers, deviceBytes} */
+static napi_value js_committee_group_info(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  bls_handle* h = argc >= 2 ? get_handle(env, argv[0]) : NULL;
+  uint32_t group = 0;
+  if (!h || napi_get_value_uint32(env, argv[1], &group) != napi_ok) {
+    napi_throw_type_error(env, NULL, "committeeGroupInfo(handle, group)");
+    return NULL;
+  }
+  bls_committee_info ci;
+  if (bls_gpu_committee_group_info(h->ctx, group, &ci) != 0) {
+    napi_throw_error(env, NULL, bls_gpu_last_error(h->ctx));
+    return NULL;
+  }
+  const char* names[3] = {"nCommittees", "nMembers", "deviceBytes"};
+  const double vals[3] = {(double)ci.n_committees, (double)ci.n_members, (double)ci.device_bytes};
+  napi_value obj;
+  CHECK(env, napi_create_object(env, &obj));
+  for (int i = 0; i < 3; ++i) {
+    napi_value v;
+    CHECK(env, napi_create_double(env, vals[i], &v));
+    CHECK(env, napi_set_named_property(env, obj, names[i], v));
+  }
+  return obj;
 }
 
 /* verifySameMessage(handle, {jobSetOffsets, messages, pkIndices, signatures, seed?}) ->
@@ -696,6 +815,9 @@ static napi_value module_init(napi_env env, napi_value exports) {
       {"finalCheck", NULL, js_final_check, NULL, NULL, NULL, napi_default, NULL},
       {"verifySameMessage", NULL, js_verify_same_message, NULL, NULL, NULL, napi_default, NULL},
       {"verifyDeposits", NULL, js_verify_deposits, NULL, NULL, NULL, napi_default, NULL},
+      {"verifyCommittees", NULL, js_verify_committees, NULL, NULL, NULL, napi_default, NULL},
+      {"setCommitteeGroup", NULL, js_set_committee_group, NULL, NULL, NULL, napi_default, NULL},
+      {"committeeGroupInfo", NULL, js_committee_group_info, NULL, NULL, NULL, napi_default, NULL},
   };
   napi_define_properties(env, exports, sizeof(d) / sizeof(d[0]), d);
   return exports;

@@ -53,6 +53,10 @@ SYMBOLS = (
     "bls_gpu_verify_same_message",
     "bls_gpu_verify_deposits",
     "bls_gpu_aggregate_pubkeys",
+    "bls_gpu_set_committee_group",
+    "bls_gpu_committee_group_info",
+    "bls_gpu_verify_committees",
+    "bls_gpu_aggregate_committee_bits",
     "bls_gpu_validate_pubkeys",
     "bls_gpu_partial",
     "bls_gpu_final_check",
@@ -78,6 +82,17 @@ SYMBOLS = (
     "bls_gpu_set_scratch_budget",
     "bls_gpu_request_hw_queues",
 )
+# committee groups (bls_gpu_set_committee_group, bls_gpu_verify_committees)
+COMMITTEE_GROUPS = 8  # BLS_COMMITTEE_GROUPS
+COMMITTEE_MAX_MEMBERS = 131072  # BLS_COMMITTEE_MAX_MEMBERS
+SET_NO_COMMITTEE = 0xFFFFFFFF  # BLS_SET_NO_COMMITTEE
+
+
+def COMMITTEE_REF(group: int, index: int) -> int:
+    """BLS_COMMITTEE_REF: committee `index` (< 2^24) of group `group`"""
+    return ((group << 24) | index) & 0xFFFFFFFF
+
+
 ERR_ADMISSION = -4  # BLS_ERR_ADMISSION: the context would push the runtime's scratch past the budget
 # SSZ kinds of bls_gpu_ssz_roots (low 8 bits: serialized size)
 SSZ_ROOT = 0x000 | 32
@@ -189,6 +204,26 @@ class BlsPubkeysInfo(ctypes.Structure):
     ]
 
 
+class BlsCommitteeInfo(ctypes.Structure):
+    """bls_committee_info: what one committee group of a context holds"""
+
+    _fields_ = [
+        ("n_committees", ctypes.c_uint32),
+        ("n_members", ctypes.c_uint32),
+        ("device_bytes", ctypes.c_uint64),
+    ]
+
+
+class BlsCommitteeSets(ctypes.Structure):
+    """bls_committee_sets: which sets of a call name a committee, and their bitfields"""
+
+    _fields_ = [
+        ("set_committee", ctypes.c_void_p),
+        ("set_bits_off", ctypes.c_void_p),
+        ("bits", ctypes.c_void_p),
+    ]
+
+
 class BlsStats(ctypes.Structure):
     _fields_ = [
         ("batch_retries", ctypes.c_uint32),
@@ -240,6 +275,15 @@ def bind(lib: ctypes.CDLL) -> ctypes.CDLL:
         lib.bls_gpu_final_check.restype = i32
         lib.bls_gpu_aggregate_pubkeys.argtypes = [vp, vp, vp, u32, vp, vp]
         lib.bls_gpu_aggregate_pubkeys.restype = i32
+        lib.bls_gpu_set_committee_group.argtypes = [vp, u32, u32, vp, vp]
+        lib.bls_gpu_set_committee_group.restype = i32
+        lib.bls_gpu_committee_group_info.argtypes = [vp, u32, ctypes.POINTER(BlsCommitteeInfo)]
+        lib.bls_gpu_committee_group_info.restype = i32
+        lib.bls_gpu_verify_committees.argtypes = [vp, ctypes.POINTER(BlsBatch), ctypes.POINTER(BlsCommitteeSets), vp,
+                                                  ctypes.POINTER(BlsStats)]
+        lib.bls_gpu_verify_committees.restype = i32
+        lib.bls_gpu_aggregate_committee_bits.argtypes = [vp, ctypes.POINTER(BlsCommitteeSets), u32, vp, vp]
+        lib.bls_gpu_aggregate_committee_bits.restype = i32
         lib.bls_gpu_g2_decompress.argtypes = [vp, vp, u32, i32, vp, vp]
         lib.bls_gpu_g2_decompress.restype = i32
         lib.bls_gpu_aggregate_signatures.argtypes = [vp, vp, vp, u32, vp, vp]

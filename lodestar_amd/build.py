@@ -326,6 +326,13 @@ def build_pk_table_host(verbose: bool = True, out: Path | None = None, extra: li
     return _build_host_program("pk_table_host", (), verbose, out, ["-pthread"] + (extra or []))
 
 
+def build_committee_host(verbose: bool = True, out: Path | None = None, extra: list[str] | None = None) -> Path:
+    """The committee groups' bookkeeping and selection rules (bls/committee.hpp) over a counting
+    host allocator and integer stand-ins for points (tests/native/committee_host.cpp), a
+    stand-alone program for tests/; `extra` as above."""
+    return _build_host_program("committee_host", (), verbose, out, extra)
+
+
 def build_cpu_baseline(verbose: bool = True) -> Path:
     """The C++ CPU baseline under oracle/cpu (benchmark / test infrastructure, "not
     blst"; oracle/cpu/bls_cpu.cpp), next to its source: bench.py's cpu_baseline leg
@@ -372,4 +379,5 @@ if __name__ == "__main__":
     build_deposit_host()
     build_comb_host()
     build_pk_table_host()
+    build_committee_host()
     build_cpu_baseline()

@@ -24,6 +24,7 @@
 #pragma once
 
 #include "../../../include/lodestar_bls.h"
+#include "committee.hpp"
 #include "hash_to_curve.hpp"
 #include "pairing.hpp"
 #include "plan_shape.hpp"
@@ -57,6 +58,16 @@ struct PipeBufs {
   // k_pk_agg (a lane per key stride, then a tree over the lanes); stage_pk skips them
   const uint32_t* agg_sets;    // n_agg set indices
   uint32_t n_agg, agg_min;
+  // committee sets (bls/committee.hpp; all null / 0: the call has none): set i names the
+  // committee set_committee[i] (BLS_SET_NO_COMMITTEE: an index-list set as above) and carries
+  // bits[set_bits_off[i], set_bits_off[i + 1]); k_pk_bits sums them one wavefront per set
+  // (bits_sets: their n_bits set indices) and stage_pk skips them
+  const CommitteeGroupDev* cm_groups;  // BLS_COMMITTEE_GROUPS
+  const uint32_t* set_committee;
+  const uint32_t* set_bits_off;
+  const uint8_t* bits;
+  const uint32_t* bits_sets;
+  uint32_t n_bits;
   const uint8_t* msgs;         // n_sets * 32
   const uint8_t* sigs;         // n_sets * 96
   const uint32_t* sig_lens;    // nullable
@@ -202,6 +213,7 @@ BLS_HD void stage_pk(const PipeBufs& b, uint32_t i) {
   if (i >= b.n_sets) return;
   int32_t code = BLS_OK;
   G1J acc = jac_infinity<Fp>();
+  if (b.set_committee && b.set_committee[i] != BLS_SET_NO_COMMITTEE) return;  // k_pk_bits sums it
   if (b.set_pk_off) {
     uint32_t beg = b.set_pk_off[i], end = b.set_pk_off[i + 1];
     if (b.agg_min && end - beg >= b.agg_min) return;  // k_pk_agg sums it
@@ -227,6 +239,7 @@ BLS_HD void stage_pk(const PipeBufs& b, uint32_t i) {
 
 // The comb rows [r] pk of set i may use, or nullptr (the GLV chain on b.pk[i]): the set
 // has exactly one table key, and that key has rows.  (Plain pointers: see k_chain's roles.)
+// A committee set's index list is empty (bls_gpu_verify_committees), so it is never one.
 BLS_HD const Fp* set_comb_rows(const uint32_t* set_pk_off, const uint32_t* pk_idx, const Fp* comb,
                                const uint8_t* comb_ok, uint32_t comb_n, uint32_t i) {
   if (!comb || !set_pk_off) return nullptr;

@@ -52,6 +52,7 @@
 #include <string>
 #include <vector>
 
+#include "bls/committee.hpp"
 #include "bls/deposit.hpp"
 #include "bls/group_decode.hpp"
 #include "bls/knobs.hpp"
@@ -82,6 +83,10 @@ struct bls_gpu_ctx {
   // (the struct is zeroed at creation).  An entry point that hands table pointers to a
   // kernel takes one snapshot and uses only that (pk_snapshot).
   std::shared_ptr<PkTable>* pkt;
+  // Committee groups (bls/committee.hpp): the slots' bookkeeping on the host and the eight
+  // views the kernels read, in device memory (all zero until a group is registered).
+  CommitteeSlots* cm;
+  CommitteeGroupDev* cm_dev;
   uint32_t debug_flags;  // bls_gpu_set_debug_flags
   // the context's last pass failed its merged check: its next pass keeps the per-set
   // [r] sig chains rather than the Pippenger sum (plan_pass: PassShape::use_msm), so a failure
@@ -191,6 +196,7 @@ extern "C" void bls_gpu_close(bls_gpu_ctx* ctx);
 static bool pk_comb_on();  // $BLS_PK_COMB (the comb rows of the table's keys, below)
 static void pk_table_new(bls_gpu_ctx* ctx);
 static void pk_table_release(bls_gpu_ctx* ctx);
+static CommitteeSlots* committee_slots_new();
 
 // ---------------------------------------------------------------------------
 // cooperative program tables: lodestar_amd/_native/coop_tables.bin next to this
@@ -576,6 +582,10 @@ int bls_gpu_init_priority(int device, int priority, bls_gpu_ctx** out) {
   if ((e = hipMalloc(&ctx->msm_state, sizeof(uint32_t) * MSM_STATE_WORDS)) != hipSuccess ||
       (e = hipMemset(ctx->msm_state, 0, sizeof(uint32_t) * MSM_STATE_WORDS)) != hipSuccess)
     return fail("msm_state", e);
+  if ((e = hipMalloc(&ctx->cm_dev, sizeof(CommitteeGroupDev) * BLS_COMMITTEE_GROUPS)) != hipSuccess ||
+      (e = hipMemset(ctx->cm_dev, 0, sizeof(CommitteeGroupDev) * BLS_COMMITTEE_GROUPS)) != hipSuccess)
+    return fail("committee groups", e);
+  ctx->cm = committee_slots_new();
   pk_table_new(ctx);
   *out = ctx;
   return 0;
@@ -593,6 +603,8 @@ void bls_gpu_close(bls_gpu_ctx* ctx) {
   }
   (void)hipSetDevice(ctx->device);
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
+  delete ctx->cm;  // every group's allocation
+  if (ctx->cm_dev) (void)hipFree(ctx->cm_dev);
   pk_table_release(ctx);  // the table goes with its last context
   if (ctx->dev_ws) (void)hipFree(ctx->dev_ws);
   if (ctx->host_stage) (void)hipHostFree(ctx->host_stage);
@@ -840,6 +852,57 @@ int bls_gpu_validate_pubkeys(bls_gpu_ctx* ctx, const uint8_t* pks, uint32_t n, u
   return 0;
 }
 
+// ---------------------------------------------------------------------------
+// committee groups (bls/committee.hpp)
+// ---------------------------------------------------------------------------
+static CommitteeSlots* committee_slots_new() { return new CommitteeSlots(&g_pk_mem, sizeof(G1J)); }
+
+extern "C" int bls_gpu_set_committee_group(bls_gpu_ctx* ctx, uint32_t group, uint32_t n, const uint32_t* member_offsets,
+                                           const uint32_t* members) {
+  if (!ctx) return -2;
+  CTX_LOCK(ctx);
+  // the table as it is now: append-only, so what is below n stays put under the totals
+  const PkView pk = pk_snapshot(ctx);
+  if (const int rc = committee_check_group(group, n, member_offsets, members, pk.snap.n, ctx->err, sizeof(ctx->err)))
+    return rc;
+  HIPC(ctx, hipSetDevice(ctx->device));
+  const hipStream_t s = ctx->stream;
+  const auto upload = [&](void* dst, const void* src, size_t bytes) {
+    return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s) == hipSuccess &&
+           hipStreamSynchronize(s) == hipSuccess;  // (the caller's arrays are pageable: done before the return)
+  };
+  const auto totals = [&](const CommitteeGroupDev& v) {
+    return launch_k_committee_totals(v, (G1J*)v.totals, pk.table(), pk.snap.n, s) == hipSuccess &&
+           hipStreamSynchronize(s) == hipSuccess;
+  };
+  const char* what = nullptr;
+  // the slot is swapped (and the old allocation freed) only by a set() that succeeded, and
+  // the stream is idle under the lock, so no kernel reads the views while they change
+  if (ctx->cm->set(group, n, member_offsets, members, upload, totals, &what) != 0) {
+    (void)hipGetLastError();
+    (void)hipStreamSynchronize(s);
+    snprintf(ctx->err, sizeof(ctx->err), "bls_gpu_set_committee_group: %s failed", what ? what : "a step");
+    return -1;
+  }
+  CommitteeGroupDev views[BLS_COMMITTEE_GROUPS];
+  ctx->cm->views(views);
+  HIPC(ctx, hipMemcpyAsync(ctx->cm_dev, views, sizeof(views), hipMemcpyHostToDevice, s));
+  HIPC(ctx, hipStreamSynchronize(s));
+  return 0;
+}
+
+extern "C" int bls_gpu_committee_group_info(bls_gpu_ctx* ctx, uint32_t group, bls_committee_info* out) {
+  if (!ctx || !out) return -2;
+  CTX_LOCK(ctx);
+  if (group >= BLS_COMMITTEE_GROUPS) {
+    snprintf(ctx->err, sizeof(ctx->err), "committee group %u: only groups 0..%u exist", group,
+             BLS_COMMITTEE_GROUPS - 1u);
+    return -2;
+  }
+  *out = ctx->cm->info(group);
+  return 0;
+}
+
 // $BLS_DEBUG_SYNC: synchronise after every kernel of a verify call and log its name
 // and wall time to stderr (a kernel that never finishes is the last name printed)
 static void dbg_sync(hipStream_t s, const char* what) {
@@ -936,6 +999,8 @@ struct PassArgs {
   const bls_deposit_batch* dep;
   // the call's snapshot of the pubkey table (nullptr for a deposit call: no table)
   const PkView* pk;
+  // verify_committees: which sets name a committee, and their bits (nullptr: none does)
+  const bls_committee_sets* cs;
 };
 
 // One verify call's pass over the device: shape and plans fixed at construction, buffers
@@ -979,6 +1044,7 @@ struct VerifyPass {
   bool gsums = false;   // group sums: the group tests pair one signature sum per test (group_sums)
   uint32_t n_sum = 0;   // requests pairing their own signature sum: iv.reqs[0, n_sum)
   std::vector<int32_t> indiv_verdict;
+  std::vector<uint32_t> bits_list;  // the committee sets (k_pk_bits), a.cs
   FoldPlan fold;        // outlive the kernels that read them from the staging area
   GsumPlan indiv_gsum;
 
@@ -992,6 +1058,9 @@ struct VerifyPass {
     memset(&g, 0, sizeof(g));
     memset(&msm, 0, sizeof(msm));
     memset(&dep, 0, sizeof(dep));
+    if (a.cs)
+      for (uint32_t i = 0; i < sh.n; ++i)
+        if (a.cs->set_committee[i] != BLS_SET_NO_COMMITTEE) bits_list.push_back(i);
   }
 
   // ---- workspace: inputs first (they live in the mapped staging area), then intermediates.
@@ -1007,6 +1076,12 @@ struct VerifyPass {
     b.set_pk_off = in->set_pk_offsets ? c.take<uint32_t>(n + 1) : nullptr;
     b.pk_idx = in->set_pk_offsets ? c.take<uint32_t>(sh.n_pk_idx) : nullptr;
     b.agg_sets = pl.agg_list.empty() ? nullptr : c.take<uint32_t>(pl.agg_list.size());
+    if (!bits_list.empty()) {
+      b.set_committee = c.take<uint32_t>(n);
+      b.set_bits_off = c.take<uint32_t>(n + 1);
+      b.bits = c.take<uint8_t>(a.cs->set_bits_off[n]);
+      b.bits_sets = c.take<uint32_t>(bits_list.size());
+    }
     b.msgs = sh.dep ? nullptr : c.take<uint8_t>(32ull * n);  // (a deposit call: device memory, below)
     if (sh.dep) {
       dep.pubkeys48 = c.take<uint8_t>(48ull * n);
@@ -1115,6 +1190,10 @@ struct VerifyPass {
     b.n_agg = (uint32_t)pl.agg_list.size();
     b.agg_min = pl.agg_list.empty() ? 0u : BLS_AGG_WAVE_MIN;
     b.n_uniq = sh.dedup ? sh.n_uniq : 0;
+    if (!bits_list.empty()) {
+      b.cm_groups = ctx->cm_dev;
+      b.n_bits = (uint32_t)bits_list.size();
+    }
   }
 
   template <class T>
@@ -1141,6 +1220,7 @@ struct VerifyPass {
     stage_vec(b.chunk_off, plan.chunk_off);
     stage_vec(b.chunk_reqs, plan.chunk_reqs);
     if (!pl.agg_list.empty()) stage_vec(b.agg_sets, pl.agg_list);
+    if (!bits_list.empty()) stage_vec(b.bits_sets, bits_list);
     if (sh.dedup) {
       stage_vec(b.msg_uniq, pl.msg_uniq);
       stage_vec(b.msg_rep, pl.msg_rep);
@@ -1155,6 +1235,11 @@ struct VerifyPass {
     if (b.set_pk_off) {
       stage_copy(ctx, b.set_pk_off, in->set_pk_offsets, sizeof(uint32_t) * (n + 1));
       stage_copy(ctx, b.pk_idx, in->pk_indices, sizeof(uint32_t) * sh.n_pk_idx);
+    }
+    if (!bits_list.empty()) {
+      stage_copy(ctx, b.set_committee, a.cs->set_committee, sizeof(uint32_t) * n);
+      stage_copy(ctx, b.set_bits_off, a.cs->set_bits_off, sizeof(uint32_t) * (n + 1));
+      stage_copy(ctx, b.bits, a.cs->bits, a.cs->set_bits_off[n]);
     }
     if (sh.dep) {
       stage_copy(ctx, dep.pubkeys48, a.dep->pubkeys48, 48ull * n);
@@ -1242,7 +1327,8 @@ struct VerifyPass {
       HIPC(ctx, launch_k_deposit(b, dep, s)); dbg_sync(s, "k_deposit");
     } else {
       HIPC(ctx, launch_k_pk(b, s));
-      HIPC(ctx, launch_k_pk_agg(b, s)); dbg_sync(s, "k_pk");
+      HIPC(ctx, launch_k_pk_agg(b, s));
+      HIPC(ctx, launch_k_pk_bits(b, s)); dbg_sync(s, "k_pk");
     }
     ctx->first_bad_slot ^= 1u;
     HIPC(ctx, hipEventRecord(ctx->ev[1], s));
@@ -1794,7 +1880,8 @@ int verify_body(bls_gpu_ctx* ctx, const bls_batch* in, const PassArgs& a) {
 static int verify_impl(bls_gpu_ctx* ctx, const bls_batch* in, int32_t* verdicts, bls_stats* stats,
                        uint32_t scalar_base, uint8_t* partial_out, int32_t* partial_status,
                        uint32_t* partial_err = nullptr, const std::vector<uint32_t>* req_bounds = nullptr,
-                       const SameMsgPlan* sm = nullptr, const bls_deposit_batch* dep = nullptr) {
+                       const SameMsgPlan* sm = nullptr, const bls_deposit_batch* dep = nullptr,
+                       const bls_committee_sets* cs = nullptr) {
   CTX_LOCK(ctx);
   ctx->wait_block = wait_blocks(knobs(), in->n_sets);
   // the table as this call sees it: kept until the stream is idle (every stage of a pass
@@ -1803,7 +1890,7 @@ static int verify_impl(bls_gpu_ctx* ctx, const bls_batch* in, int32_t* verdicts,
   PkView pk;
   if (!dep) pk = pk_snapshot(ctx);
   const int rc = verify_body(ctx, in, PassArgs{verdicts, stats, scalar_base, partial_out, partial_status, partial_err,
-                                               req_bounds, sm, dep, dep ? nullptr : &pk});
+                                               req_bounds, sm, dep, dep ? nullptr : &pk, cs});
   if (rc != 0) (void)hipStreamSynchronize(ctx->stream);
   if (rc < 0 && ctx->msm_state) {
     (void)hipMemsetAsync(ctx->msm_state, 0, sizeof(uint32_t) * MSM_STATE_WORDS, ctx->stream);
@@ -1816,6 +1903,20 @@ extern "C" {
 
 int bls_gpu_verify(bls_gpu_ctx* ctx, const bls_batch* in, int32_t* verdicts, bls_stats* stats) {
   return verify_impl(ctx, in, verdicts, stats, 0u, nullptr, nullptr);
+}
+
+int bls_gpu_verify_committees(bls_gpu_ctx* ctx, const bls_batch* in, const bls_committee_sets* cs, int32_t* verdicts,
+                              bls_stats* stats) {
+  if (!ctx || !in) return -2;
+  {
+    CTX_LOCK(ctx);  // (for ctx->err; verify_impl takes the lock for the call itself)
+    if (in->n_sets && !in->set_pk_offsets) {
+      snprintf(ctx->err, sizeof(ctx->err), "committee sets: the batch must carry table indices (set_pk_offsets)");
+      return -2;
+    }
+    if (const int rc = committee_check_sets(cs, in->n_sets, in->set_pk_offsets, ctx->err, sizeof(ctx->err))) return rc;
+  }
+  return verify_impl(ctx, in, verdicts, stats, 0u, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, cs);
 }
 
 int bls_gpu_verify_many(bls_gpu_ctx* ctx, const bls_batch* batches, uint32_t n_batches, int32_t* verdicts,
@@ -2049,6 +2150,68 @@ int bls_gpu_aggregate_pubkeys(bls_gpu_ctx* ctx, const uint32_t* set_pk_offsets, 
     HIPC(ctx, launch_k_pk_agg(b, s));  // the big aggregates first; k_aggregate serializes every set
   }
   HIPC(ctx, launch_k_aggregate(b, d_out, s));
+  HIPC(ctx, hipMemcpyAsync(out96, d_out, 96ull * n_sets, hipMemcpyDeviceToHost, s));
+  if (codes) HIPC(ctx, hipMemcpyAsync(codes, b.pk_status, sizeof(int32_t) * n_sets, hipMemcpyDeviceToHost, s));
+  HIPC(ctx, hipStreamSynchronize(s));
+  drain.armed = false;
+  return 0;
+}
+
+int bls_gpu_aggregate_committee_bits(bls_gpu_ctx* ctx, const bls_committee_sets* cs, uint32_t n_sets, uint8_t* out96,
+                                     int32_t* codes) {
+  if (!ctx) return -2;
+  CTX_LOCK(ctx);
+  if (const int rc = committee_check_sets(cs, n_sets, nullptr, ctx->err, sizeof(ctx->err))) return rc;
+  if (n_sets && !out96) return -2;
+  for (uint32_t i = 0; i < n_sets; ++i)
+    if (cs->set_committee[i] == BLS_SET_NO_COMMITTEE) {
+      snprintf(ctx->err, sizeof(ctx->err), "committee sets: set %u names no committee", i);
+      return -2;
+    }
+  HIPC(ctx, hipSetDevice(ctx->device));
+  if (n_sets == 0) return 0;
+  const uint32_t n_bytes = cs->set_bits_off[n_sets];
+  PipeBufs b;
+  memset(&b, 0, sizeof(b));
+  auto carve = [&](Carver& c, uint8_t*& d_out) {
+    b.set_committee = c.take<uint32_t>(n_sets);
+    b.set_bits_off = c.take<uint32_t>(n_sets + 1);
+    b.bits = c.take<uint8_t>(n_bytes);
+    b.bits_sets = c.take<uint32_t>(n_sets);
+    b.pk = c.take<G1J>(n_sets);
+    b.pk_status = c.take<int32_t>(n_sets);
+    d_out = c.take<uint8_t>(96ull * n_sets);
+  };
+  uint8_t* d_out = nullptr;
+  {
+    Carver c{nullptr, 0};
+    carve(c, d_out);
+    if (ensure_dev(ctx, c.off)) return -1;
+  }
+  Carver c{ctx->dev_ws, 0};
+  carve(c, d_out);
+  b.n_sets = b.n_bits = n_sets;
+  b.cm_groups = ctx->cm_dev;
+  const PkView pk = pk_snapshot(ctx);  // dropped at return; an error path waits first (below)
+  b.pk_table = pk.table();
+  b.pk_table_n = pk.snap.n;
+  std::vector<uint32_t> all(n_sets);
+  for (uint32_t i = 0; i < n_sets; ++i) all[i] = i;
+  hipStream_t s = ctx->stream;
+  struct Drain {  // a failed copy or launch leaves earlier kernels on the stream
+    hipStream_t s;
+    bool armed;
+    ~Drain() {
+      if (armed) (void)hipStreamSynchronize(s);
+    }
+  } drain{s, true};
+  HIPC(ctx, hipMemcpyAsync((void*)b.set_committee, cs->set_committee, sizeof(uint32_t) * n_sets, hipMemcpyHostToDevice, s));
+  HIPC(ctx, hipMemcpyAsync((void*)b.set_bits_off, cs->set_bits_off, sizeof(uint32_t) * (n_sets + 1),
+                           hipMemcpyHostToDevice, s));
+  if (n_bytes) HIPC(ctx, hipMemcpyAsync((void*)b.bits, cs->bits, n_bytes, hipMemcpyHostToDevice, s));
+  HIPC(ctx, hipMemcpyAsync((void*)b.bits_sets, all.data(), sizeof(uint32_t) * n_sets, hipMemcpyHostToDevice, s));
+  HIPC(ctx, launch_k_pk_bits(b, s));
+  HIPC(ctx, launch_k_aggregate(b, d_out, s));  // stage_pk skips every set; it serializes them
   HIPC(ctx, hipMemcpyAsync(out96, d_out, 96ull * n_sets, hipMemcpyDeviceToHost, s));
   if (codes) HIPC(ctx, hipMemcpyAsync(codes, b.pk_status, sizeof(int32_t) * n_sets, hipMemcpyDeviceToHost, s));
   HIPC(ctx, hipStreamSynchronize(s));

@@ -1,5 +1,6 @@
-// Pubkey stage: deserialize raw 96-byte keys or sum device-table keys (aggregate sets),
-// plus the pubkey-table loader and the per-request status pass (small kernels).
+// Pubkey stage: deserialize raw 96-byte keys or sum device-table keys (aggregate sets given
+// as index lists, or as a registered committee and its participation bits), plus the
+// pubkey-table loader and the per-request status pass (small kernels).
 #include "../launchers.hpp"
 
 using namespace bls;
@@ -57,6 +58,129 @@ __global__ __launch_bounds__(BLS_BLOCK) void k_pk_agg(PipeBufs b) {
 hipError_t launch_k_pk_agg(const PipeBufs& b, hipStream_t s) {
   if (b.n_agg == 0) return hipSuccess;
   k_pk_agg<<<b.n_agg, BLS_BLOCK, 0, s>>>(b);
+  return hipGetLastError();
+}
+
+// The selected members of one committee summed by a wavefront (bls/committee.hpp): position
+// j of mem[0, n) is summed when bits is null (every member: a committee's total) or
+// committee_selects(bits, j, comp).  The selected positions are compacted round by round --
+// a ballot over 64 positions, each selected lane's rank by the prefix count -- into a
+// 128-entry ring in LDS that the lanes drain 64 at a time, so a lane does at most
+// ceil(selected / 64) mixed additions wherever the bits fall (a lane per position would
+// hand one lane every selected member of a field whose set bits lie 64 apart).  Then
+// k_pk_agg's six-level tree; part[0] holds the sum.  Every loop bound is uniform over the wavefront.  bad: a member at or past
+// the table (registration rules it out; the read is not made).
+__device__ __forceinline__ void committee_wave_sum(G1J* part, uint32_t* ring, const uint32_t* mem, uint32_t n,
+                                                   const uint8_t* bits, bool comp, const G1A* table, uint32_t table_n,
+                                                   bool& bad) {
+  const uint32_t lane = threadIdx.x;
+  G1J acc = jac_infinity<Fp>();
+  uint32_t pending = 0;
+  for (uint32_t base = 0; base < n; base += BLS_BLOCK) {
+    const uint32_t j = base + lane;
+    const bool sel = j < n && (!bits || committee_selects(bits, j, comp));
+    const uint64_t mask = __ballot(sel);
+    if (sel) ring[pending + __popcll(mask & ((1ull << lane) - 1ull))] = mem[j];
+    pending += __popcll(mask);  // <= 63 + 64: the ring holds 128
+    __syncthreads();
+    if (pending >= BLS_BLOCK) {
+      const uint32_t idx = ring[lane];
+      const uint32_t rest = pending - BLS_BLOCK;
+      const uint32_t carry = lane < rest ? ring[BLS_BLOCK + lane] : 0u;
+      __syncthreads();
+      if (lane < rest) ring[lane] = carry;
+      pending = rest;
+      if (idx >= table_n) bad = true;
+      else acc = jac_add_aff(acc, table[idx]);
+      __syncthreads();
+    }
+  }
+  if (lane < pending) {
+    const uint32_t idx = ring[lane];
+    if (idx >= table_n) bad = true;
+    else acc = jac_add_aff(acc, table[idx]);
+  }
+  part[lane] = acc;
+  __syncthreads();
+  for (uint32_t s = BLS_BLOCK / 2; s >= 1; s >>= 1) {
+    if (lane < s) part[lane] = jac_add(part[lane], part[lane + s]);
+    __syncthreads();
+  }
+}
+
+// A committee set (b.bits_sets; bls_gpu_verify_committees) = the aggregate set whose index
+// list is the committee's members at the set bits: one wavefront per set.  The lanes count
+// the set bits, committee_use_complement picks the cheaper form -- the members whose bit is
+// set, or the committee's total minus the members whose bit is clear -- and lane 0 writes
+// what k_pk_agg writes.  The group law's edges are jac_add's: a complement equal to the
+// total gives infinity, a duplicated member doubles.
+__global__ __launch_bounds__(BLS_BLOCK) void k_pk_bits(PipeBufs b) {
+  __shared__ G1J part[BLS_BLOCK];
+  __shared__ uint32_t ring[2 * BLS_BLOCK];
+  const uint32_t lane = threadIdx.x;
+  const uint32_t i = b.bits_sets[blockIdx.x];
+  const uint32_t ref = b.set_committee[i];
+  const uint32_t g = committee_ref_group(ref), ci = committee_ref_index(ref);
+  int32_t code = BLS_OK;
+  G1J sum = jac_infinity<Fp>();
+  if (g >= BLS_COMMITTEE_GROUPS || !b.cm_groups[g].offsets || ci >= b.cm_groups[g].n) {
+    code = BLS_BAD_ENCODING;  // an unregistered group, an index past the group
+  } else {
+    const CommitteeGroupDev grp = b.cm_groups[g];
+    const uint32_t beg = grp.offsets[ci], n = grp.offsets[ci + 1] - beg;
+    const uint32_t boff = b.set_bits_off[i];
+    const uint8_t* bits = b.bits + boff;
+    code = committee_check_bits(bits, b.set_bits_off[i + 1] - boff, n);
+    if (code == BLS_OK) {
+      uint32_t c = 0;
+      for (uint32_t base = 0; base < n; base += BLS_BLOCK) {
+        const uint32_t j = base + lane;
+        c += __popcll(__ballot(j < n && committee_bit(bits, j)));
+      }
+      if (c == 0) {
+        code = BLS_EMPTY_AGGREGATE;
+      } else {
+        const bool comp = committee_use_complement(n, c);
+        bool bad = false;
+        committee_wave_sum(part, ring, grp.members + beg, n, bits, comp, b.pk_table, b.pk_table_n, bad);
+        if (__any(bad)) code = BLS_BAD_ENCODING;
+        if (lane == 0) {
+          sum = part[0];
+          if (comp) sum = jac_add(static_cast<const G1J*>(grp.totals)[ci], jac_neg(sum));
+        }
+      }
+    }
+  }
+  if (lane == 0) {
+    b.pk[i] = sum;
+    b.pk_status[i] = code;
+    if (b.pk_inf) b.pk_inf[i] = (code == BLS_OK && jac_is_inf(sum)) ? 1 : 0;
+  }
+}
+
+hipError_t launch_k_pk_bits(const PipeBufs& b, hipStream_t s) {
+  if (b.n_bits == 0) return hipSuccess;
+  k_pk_bits<<<b.n_bits, BLS_BLOCK, 0, s>>>(b);
+  return hipGetLastError();
+}
+
+// Registration of a committee group (bls_gpu_set_committee_group): committee blockIdx.x's
+// total, the sum over all of its members with multiplicity.
+__global__ __launch_bounds__(BLS_BLOCK) void k_committee_totals(CommitteeGroupDev grp, G1J* totals, const G1A* table,
+                                                                uint32_t table_n) {
+  __shared__ G1J part[BLS_BLOCK];
+  __shared__ uint32_t ring[2 * BLS_BLOCK];
+  const uint32_t ci = blockIdx.x;
+  const uint32_t beg = grp.offsets[ci], n = grp.offsets[ci + 1] - beg;
+  bool bad = false;
+  committee_wave_sum(part, ring, grp.members + beg, n, nullptr, false, table, table_n, bad);
+  if (threadIdx.x == 0) totals[ci] = part[0];
+}
+
+hipError_t launch_k_committee_totals(const CommitteeGroupDev& grp, G1J* totals, const G1A* table, uint32_t table_n,
+                                     hipStream_t s) {
+  if (grp.n == 0) return hipSuccess;
+  k_committee_totals<<<grp.n, BLS_BLOCK, 0, s>>>(grp, totals, table, table_n);
   return hipGetLastError();
 }
 

@@ -19,6 +19,10 @@ static inline unsigned bls_grid_for(uint32_t n) { return (n + BLS_BLOCK - 1) / B
 
 hipError_t launch_k_pk(const bls::PipeBufs& b, hipStream_t s);
 hipError_t launch_k_pk_agg(const bls::PipeBufs& b, hipStream_t s);
+// committee sets (bls/committee.hpp): b.bits_sets' sums, and a group's totals at registration
+hipError_t launch_k_pk_bits(const bls::PipeBufs& b, hipStream_t s);
+hipError_t launch_k_committee_totals(const bls::CommitteeGroupDev& grp, bls::G1J* totals, const bls::G1A* table,
+                                     uint32_t table_n, hipStream_t s);
 hipError_t launch_k_aggregate(const bls::PipeBufs& b, uint8_t* out96, hipStream_t s);
 hipError_t launch_k_load_pubkeys(const uint8_t* pks, uint32_t n, uint32_t pk_len, bls::G1A* out, int32_t* codes,
                                  hipStream_t s);

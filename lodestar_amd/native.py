@@ -12,7 +12,8 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from ._abi import ERR_ADMISSION, BlsAdmission, BlsBatch, BlsDepositBatch, BlsSameMsgBatch, BlsStats, load_library
+from ._abi import (COMMITTEE_REF, ERR_ADMISSION, SET_NO_COMMITTEE, BlsAdmission, BlsBatch, BlsCommitteeInfo,
+                   BlsCommitteeSets, BlsDepositBatch, BlsSameMsgBatch, BlsStats, load_library)
 
 
 def _ptr(a: np.ndarray | None):
@@ -100,6 +101,10 @@ class PackedBatch:
     pk_indices: np.ndarray | None = None  # uint32[...]
     signature_lens: np.ndarray | None = None  # uint32[n_sets]
     seed: bytes | None = None
+    # committee sets (bls_committee_sets; None: the batch has none and goes to bls_gpu_verify)
+    set_committee: np.ndarray | None = None  # uint32[n_sets]: COMMITTEE_REF or SET_NO_COMMITTEE
+    set_bits_off: np.ndarray | None = None  # uint32[n_sets + 1] byte offsets into bits
+    bits: np.ndarray | None = None  # uint8[...]
     # the bls_batch view of these arrays, built on first use (GpuContext._batch_struct):
     # a pass of 64 calls re-packed its 64 structs under the GIL at every submission
     _cstruct: object = field(default=None, repr=False, compare=False)
@@ -118,15 +123,31 @@ def pack_requests(requests, seed: bytes | None = None) -> PackedBatch:
 
     pk is either 96 raw bytes (uncompressed affine) or a list/tuple of device
     pubkey-table indices (all sets of one batch must use the same form).  sig may
-    have any length (a length other than 96 yields BLST_INVALID_SIZE)."""
+    have any length (a length other than 96 yields BLST_INVALID_SIZE).
+
+    A set may also be a dict {"committee": (group, index), "bits": bytes, "message": msg32,
+    "signature": sig}: the aggregate of a registered committee's members at the set bits
+    (GpuContext.set_committee_group).  Such sets mix with index-list sets, not with raw
+    keys, and the batch then goes through GpuContext.verify_committees_packed."""
     offs = [0]
     batchable = []
     msgs, sigs, lens = [], [], []
     raw_pks, idx_offs, idx = [], [0], []
     table_mode = None
+    refs, bits_offs, bits = [], [0], []
     for is_b, sets in requests:
         batchable.append(1 if is_b else 0)
-        for pk, msg, sig in sets:
+        for one in sets:
+            if isinstance(one, dict):
+                group, index = one["committee"]
+                pk, msg, sig = (), one["message"], one["signature"]
+                refs.append(COMMITTEE_REF(int(group), int(index)))
+                bits.append(bytes(one["bits"]))
+            else:
+                pk, msg, sig = one
+                refs.append(SET_NO_COMMITTEE)
+                bits.append(b"")
+            bits_offs.append(bits_offs[-1] + len(bits[-1]))
             this_table = not isinstance(pk, (bytes, bytearray, memoryview, np.ndarray))
             if table_mode is None:
                 table_mode = this_table
@@ -162,6 +183,10 @@ def pack_requests(requests, seed: bytes | None = None) -> PackedBatch:
     if table_mode:
         pb.set_pk_offsets = np.array(idx_offs, dtype=np.uint32)
         pb.pk_indices = np.array(idx if idx else [0], dtype=np.uint32)
+        if any(r != SET_NO_COMMITTEE for r in refs):
+            pb.set_committee = np.array(refs, dtype=np.uint32)
+            pb.set_bits_off = np.array(bits_offs, dtype=np.uint32)
+            pb.bits = np.frombuffer(b"".join(bits) or b"\0", dtype=np.uint8).copy()
     else:
         pb.pubkeys = np.frombuffer(b"".join(raw_pks), dtype=np.uint8).copy() if n else np.zeros(96, np.uint8)
     return pb
@@ -355,6 +380,68 @@ class GpuContext:
         rc = self.lib.bls_gpu_verify(self._h, ctypes.byref(b), _ptr(verdicts), ctypes.byref(stats))
         self._check(rc, "bls_gpu_verify")
         return verdicts[: pb.n_reqs], stats
+
+    # -- committee groups -----------------------------------------------------------
+    def set_committee_group(self, group: int, committees) -> None:
+        """Register (replace) committee group `group` (0..7): `committees` is a list of member
+        lists of table indices, in committee order, duplicates allowed; an empty list drops
+        the group (bls_gpu_set_committee_group).  Raises NativeError, the group unchanged,
+        for a member past the table, an empty committee or a group past the slots."""
+        offs, mem = [0], []
+        for c in committees:
+            mem.extend(int(i) for i in c)
+            offs.append(len(mem))
+        o = np.array(offs, dtype=np.uint32)
+        m = np.array(mem if mem else [0], dtype=np.uint32)
+        rc = self.lib.bls_gpu_set_committee_group(self._h, group, len(offs) - 1, _ptr(o), _ptr(m))
+        self._check(rc, "bls_gpu_set_committee_group")
+
+    def committee_group_info(self, group: int) -> dict:
+        """n_committees, n_members and device_bytes of group `group` (all 0: not registered)."""
+        info = BlsCommitteeInfo()
+        self._check(self.lib.bls_gpu_committee_group_info(self._h, group, ctypes.byref(info)),
+                    "bls_gpu_committee_group_info")
+        return {name: int(getattr(info, name)) for name, _ in BlsCommitteeInfo._fields_}
+
+    @staticmethod
+    def _committee_struct(set_committee, set_bits_off, bits):
+        keep = [np.ascontiguousarray(set_committee, dtype=np.uint32), np.ascontiguousarray(set_bits_off, dtype=np.uint32),
+                np.ascontiguousarray(bits, dtype=np.uint8)]
+        cs = BlsCommitteeSets()
+        cs.set_committee, cs.set_bits_off, cs.bits = (_ptr(a) for a in keep)
+        return cs, keep
+
+    def verify_committees_packed(self, pb: PackedBatch) -> tuple[np.ndarray, BlsStats]:
+        """bls_gpu_verify_committees for a batch packed from requests that hold committee
+        sets (pack_requests); one without any goes to bls_gpu_verify as verify_packed does."""
+        if pb.set_committee is None:
+            return self.verify_packed(pb)
+        b, _keep = self._batch_struct(pb)
+        cs, _keep2 = self._committee_struct(pb.set_committee, pb.set_bits_off, pb.bits)
+        verdicts = np.zeros(max(pb.n_reqs, 1), dtype=np.int32)
+        stats = BlsStats()
+        rc = self.lib.bls_gpu_verify_committees(self._h, ctypes.byref(b), ctypes.byref(cs), _ptr(verdicts),
+                                                ctypes.byref(stats))
+        self._check(rc, "bls_gpu_verify_committees")
+        return verdicts[: pb.n_reqs], stats
+
+    def aggregate_committee_bits(self, sets) -> tuple[list[bytes], np.ndarray]:
+        """sets: list of ((group, index), bits).  The aggregate key of each committee's members
+        at the set bits, as aggregate_pubkeys gives it for the expanded index list: 96-byte
+        uncompressed keys and codes (bls_gpu_aggregate_committee_bits)."""
+        n = len(sets)
+        refs = [COMMITTEE_REF(int(g), int(i)) for (g, i), _ in sets]
+        offs = [0]
+        for _, bt in sets:
+            offs.append(offs[-1] + len(bytes(bt)))
+        cs, _keep = self._committee_struct(np.array(refs if refs else [0], dtype=np.uint32), np.array(offs, dtype=np.uint32),
+                                           np.frombuffer(b"".join(bytes(bt) for _, bt in sets) or b"\0", dtype=np.uint8))
+        out = np.zeros(96 * max(n, 1), dtype=np.uint8)
+        codes = np.zeros(max(n, 1), dtype=np.int32)
+        rc = self.lib.bls_gpu_aggregate_committee_bits(self._h, ctypes.byref(cs), n, _ptr(out), _ptr(codes))
+        self._check(rc, "bls_gpu_aggregate_committee_bits")
+        raw = out.tobytes()
+        return [raw[96 * i: 96 * i + 96] for i in range(n)], codes[:n]
 
     def verify_many(self, pbs: list[PackedBatch]) -> tuple[list[np.ndarray], BlsStats]:
         """Several worker messages in one submission (bls_gpu_verify_many): per-message

@@ -72,7 +72,12 @@ with GPU contexts in place of worker threads:
 Sets are `SignatureSet(pubkey, signing_root, signature)` where pubkey is an int
 index into the context's device pubkey table (Index2PubkeyCache), a list of
 indices (an aggregate set, getAggregatedPubkey, utils.ts:5-16), or 96 raw bytes
-(uncompressed affine, the worker wire format of index.ts:126).
+(uncompressed affine, the worker wire format of index.ts:126).  An aggregate set may
+also be a `CommitteeSet(group, index, bits, signing_root, signature)`: a committee of
+a group registered with `set_committee_group` -- which reaches every context of every
+device and those opened later (`add_context`) -- and its participation bits.  A job
+holding one goes out as its own bls_gpu_verify_committees message and weighs
+1 + min(c, n - c) keys per such set; split calls and same-message calls keep index lists.
 """
 from __future__ import annotations
 
@@ -105,6 +110,26 @@ class SignatureSet:
     pubkey: PubkeyRef
     signing_root: bytes
     signature: bytes
+
+
+@dataclass
+class CommitteeSet:
+    """An aggregate set as it arrives on the wire: committee `index` of the registered group
+    `group` (GpuBlsVerifier.set_committee_group) and its participation bits in SSZ order
+    (member j = bit j & 7 of byte j >> 3, no Bitlist delimiter) -- Attestation.aggregation_bits
+    over a beacon committee, SyncAggregate.sync_committee_bits over the sync committee.  It
+    verifies exactly as the SignatureSet whose pubkey lists the committee's members at the set
+    bits."""
+
+    group: int
+    index: int
+    bits: bytes
+    signing_root: bytes
+    signature: bytes
+
+
+def _popcount(bits: bytes) -> int:
+    return bin(int.from_bytes(bits, "little")).count("1") if bits else 0
 
 
 class BlsError(Exception):
@@ -162,7 +187,16 @@ def set_weight(pk) -> float:
     return 1.0 + (k / AGG_KEY_WEIGHT if k > 1 else 0.0)
 
 
-def _wire(s: SignatureSet):
+def committee_weight_keys(n_members: int, n_set: int) -> int:
+    """Keys a committee set costs its device (bls/committee.hpp committee_weight): the set bits
+    summed directly, or the clear ones taken from the committee's total"""
+    return 1 + min(n_set, max(n_members - n_set, 0))
+
+
+def _wire(s):
+    if isinstance(s, CommitteeSet):
+        return {"committee": (int(s.group), int(s.index)), "bits": bytes(s.bits), "message": bytes(s.signing_root),
+                "signature": bytes(s.signature)}
     pk = s.pubkey
     if isinstance(pk, int):
         pk = [pk]
@@ -196,6 +230,7 @@ class GpuBlsVerifier:
             raise ValueError("devices: at least one device")
         self.split_call_min_sets = max(2, int(split_call_min_sets))
         make = context_factory or (lambda dev, high: GpuContext(dev, high_priority=high))
+        self._make = make
         # the main-thread lane first (its own high-priority context, never used by the
         # pool), then the pool's contexts: a context the library refuses (scratch
         # admission, BLS_ERR_ADMISSION) or that fails to start is recorded and the pool runs
@@ -214,6 +249,7 @@ class GpuBlsVerifier:
                 except NativeError as e:
                     self.init_errors.append(e)
         self._main_lock = threading.Lock()
+        self._groups: dict[int, list] = {}  # committee groups as registered (set_committee_group)
         self._table_ctxs = self._share_tables() if share_pubkeys else None
         if pubkeys48 is not None:
             self.load_pubkeys(pubkeys48)
@@ -288,6 +324,61 @@ class GpuBlsVerifier:
             if (codes != 0).any():  # same bytes as context 0: cannot happen short of a device fault
                 raise BlsError("pubkey tables diverged across contexts")
 
+    # -- committee groups --------------------------------------------------------------
+    def set_committee_group(self, group: int, committees) -> None:
+        """Register (replace; an empty list drops) committee group `group` on every context
+        of every device: `committees` is a list of member lists of validator indices.  Groups
+        belong to a context (bls_gpu_set_committee_group), so each context gets its copy; a
+        call of a context runs either before or after its copy changes.  The first context's
+        validation decides for all: a rejected registration changes none of them."""
+        committees = [list(c) for c in committees]
+        ctxs = [self._main] + self._ctxs
+        for k, c in enumerate(ctxs):
+            try:
+                c.set_committee_group(group, committees)
+            except NativeError as e:
+                if k:  # same arrays, same table size: cannot happen short of a device fault
+                    raise BlsError(f"committee groups diverged across contexts: {e}") from e
+                raise BlsError(str(e)) from e
+        with self._cv:
+            if committees:
+                self._groups[group] = committees
+            else:
+                self._groups.pop(group, None)
+
+    def _adopt_groups(self, ctx) -> None:
+        """a context opened after the registrations gets every group"""
+        for group, committees in sorted(self._groups.items()):
+            ctx.set_committee_group(group, committees)
+
+    def add_context(self, slot: int = 0):
+        """Open one more pool context on device slot `slot`: it shares the device's key table
+        and holds every registered committee group before it takes work."""
+        ctx = self._make(self.devices[slot], False)
+        if self._table_ctxs is not None:
+            ctx.share_pubkeys(self._table_ctxs[list(dict.fromkeys(self.devices)).index(self.devices[slot])])
+        with self._cv:
+            self._adopt_groups(ctx)
+            wid = len(self._ctxs)
+            self._ctxs.append(ctx)
+            self._ctx_slot.append(slot)
+            self._slot_ctxs[slot] += 1
+            t = threading.Thread(target=self._worker, args=(ctx, slot, wid), daemon=True)
+            self._threads.append(t)
+        t.start()
+        return ctx
+
+    def _set_weight(self, wire) -> float:
+        """set_weight of a wire set; a committee set weighs 1 + min(c, n - c) keys in place of k"""
+        if not isinstance(wire, dict):
+            return set_weight(wire[0])
+        group, index = wire["committee"]
+        members = self._groups.get(group)
+        c = _popcount(wire["bits"])
+        n = len(members[index]) if members is not None and 0 <= index < len(members) else c
+        k = committee_weight_keys(n, c)
+        return 1.0 + (k / AGG_KEY_WEIGHT if k > 1 else 0.0)
+
     # -- IBlsVerifier --------------------------------------------------------------
     def verify_signature_sets(self, sets: Sequence[SignatureSet], batchable: bool = False,
                               verify_on_main_thread: bool = False) -> bool:
@@ -296,7 +387,9 @@ class GpuBlsVerifier:
     def verify_signature_sets_async(self, sets: Sequence[SignatureSet], batchable: bool = False,
                                     verify_on_main_thread: bool = False) -> Future:
         # pubkeys are aggregated (on the device) whichever branch runs (index.ts:136)
-        self.metrics.bls.aggregatedPubkeys.inc(get_aggregated_pubkeys_count(sets))
+        self.metrics.bls.aggregatedPubkeys.inc(
+            get_aggregated_pubkeys_count([s for s in sets if not isinstance(s, CommitteeSet)])
+            + sum(_popcount(bytes(s.bits)) for s in sets if isinstance(s, CommitteeSet)))
         if verify_on_main_thread and not self.verify_all_multi_thread:
             fut: Future = Future()
             stop = self.metrics.blsThreadPool.mainThreadDurationInThreadPool.start_timer()
@@ -309,7 +402,9 @@ class GpuBlsVerifier:
                 stop()
             return fut
         sets = list(sets)
+        # (a sharded call keeps index lists, as bls_gpu_partial does)
         if (not batchable and len(self.devices) > 1 and len(sets) >= self.split_call_min_sets
+                and not any(isinstance(s, CommitteeSet) for s in sets)
                 and sum(self._slot_ctxs) > 0 and all(self._slot_ctxs)):
             return self._split_call(sets)
         return self._queue_call(sets, batchable)
@@ -569,10 +664,13 @@ class GpuBlsVerifier:
 
     def _call(self, ctx, reqs, worker_id: int = 0):
         """One GPU submission per pubkey form: table-index requests as one message
-        (bls_gpu_verify), raw-key requests as the reference's worker messages (jobs until
-        >= 128 sets each) through one bls_gpu_verify_many."""
+        (bls_gpu_verify), requests holding a committee set as a message of their own
+        (bls_gpu_verify_committees), raw-key requests as the reference's worker messages (jobs
+        until >= 128 sets each) through one bls_gpu_verify_many."""
         def is_raw(req):
-            return any(isinstance(pk, (bytes, bytearray, memoryview)) for pk, _, _ in req[1])
+            if any(isinstance(s, dict) for s in req[1]):
+                return "committee"
+            return any(isinstance(s[0], (bytes, bytearray, memoryview)) for s in req[1])
         groups = {}
         for k, r in enumerate(reqs):
             groups.setdefault(is_raw(r), []).append(k)
@@ -581,7 +679,11 @@ class GpuBlsVerifier:
         tp = self.metrics.blsThreadPool
         for raw, idx in groups.items():
             t0 = time.perf_counter()
-            if raw:
+            if raw == "committee":
+                pb = pack_requests([reqs[k] for k in idx])
+                t1 = time.perf_counter()
+                v, stats = ctx.verify_committees_packed(pb)
+            elif raw:
                 msgs, cur, n = [], [], 0
                 for k in idx:
                     cur.append(k)
@@ -711,8 +813,11 @@ class GpuBlsVerifier:
                 elif dep_job is not None:
                     keys = [0] * dep_job.packed.n  # one key per deposit: each weighs one set
                 else:
-                    keys = [pk for pk, _, _ in (pin.sets if pin is not None else [s for j in jobs for s in j.sets])]
-                weight = sum(set_weight(pk) for pk in keys)
+                    keys = pin.sets if pin is not None else [s for j in jobs for s in j.sets]
+                if sm_jobs is not None or dep_job is not None:
+                    weight = sum(set_weight(pk) for pk in keys)
+                else:
+                    weight = sum(self._set_weight(w) for w in keys)
                 self._load[slot] += weight
                 st = self.slot_stats[slot]
                 st["calls"] += 1
