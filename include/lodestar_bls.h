@@ -405,6 +405,47 @@ int bls_gpu_verify_committees(bls_gpu_ctx* ctx, const bls_batch* batch, const bl
 int bls_gpu_aggregate_committee_bits(bls_gpu_ctx* ctx, const bls_committee_sets* cs, uint32_t n_sets,
                                      uint8_t* out96, int32_t* codes);
 
+/* Spans: an aggregate over several committees under one field.  Since Electra (EIP-7549) an
+ * on-chain Attestation selects up to 64 committees of its slot with committee_bits, and its
+ * aggregation_bits run over those committees' members concatenated in committee order.
+ * Committee sizes are no multiples of 8, so every committee after the first starts mid-byte
+ * and the field cannot be cut into bls_committee_sets fields.  A span set names its
+ * committees (its segments) in order and carries the field as it is: segment k of sizes
+ * n_0, n_1, ... starts at bit n_0 + ... + n_{k-1}.  Each segment by itself is summed from
+ * its set bits or as its total minus its clear bits, so a set costs
+ * sum_k min(c_k, n_k - c_k + 1) point additions.
+ *
+ * A span set is exactly the aggregate set whose index list is the members of its segments,
+ * concatenated in order, at the set bits: a one-segment span is a committee set; segments
+ * may repeat a committee and come from different groups; a key in several segments counts
+ * with multiplicity.  Its status: no bit set in the whole field BLS_CODE_EMPTY_AGGREGATE (a
+ * segment without a set bit beside one that has some is legal here -- Electra's "every
+ * selected committee has an attester" is a state-transition rule and stays with the host);
+ * a segment of an unregistered group, an index past its group, a byte count other than
+ * ceil(sum n_k / 8) or a set bit at or past sum n_k BLS_CODE_BAD_ENCODING. */
+#define BLS_SPAN_MAX_COMMITTEES 64u           /* MAX_COMMITTEES_PER_SLOT */
+typedef struct bls_span_sets {
+  const uint32_t* set_span_off;  /* n_sets + 1 into span_refs, monotone from 0; an empty range: the set
+                                    is an index-list set (batch->set_pk_offsets / pk_indices) */
+  const uint32_t* span_refs;     /* BLS_COMMITTEE_REF(group, index) per segment, in order */
+  const uint32_t* set_bits_off;  /* n_sets + 1 byte offsets into bits (equal for an index-list set) */
+  const uint8_t* bits;           /* bit j of the concatenation = bit (j & 7) of byte j >> 3; no delimiter bit */
+} bls_span_sets;
+
+/* bls_gpu_verify for a batch some of whose sets are spans: the verdicts and every bls_stats
+ * counter of bls_gpu_verify on the expanded lists with the same seed.  -2 with a
+ * bls_gpu_last_error message naming the set, and nothing run, for a set of more than
+ * BLS_SPAN_MAX_COMMITTEES segments, offsets that do not run monotonically from 0, a span
+ * set that also carries an index list, an index-list set that carries bits, a raw-key batch
+ * (set_pk_offsets == NULL), or a NULL array where one is needed. */
+int bls_gpu_verify_spans(bls_gpu_ctx* ctx, const bls_batch* batch, const bls_span_sets* ss,
+                         int32_t* verdicts, bls_stats* stats);
+/* bls_gpu_aggregate_pubkeys for n_sets span sets (every set has at least one segment, -2
+ * otherwise): the same bytes and codes as the expanded index lists give.  n_sets == 0
+ * returns 0 and writes nothing. */
+int bls_gpu_aggregate_spans(bls_gpu_ctx* ctx, const bls_span_sets* ss, uint32_t n_sets,
+                            uint8_t* out96, int32_t* codes);
+
 /* G2 signature aggregation for the op pools:
  * Signature.aggregate(sigs.map((s) => Signature.fromBytes(s, undefined, true))) for each
  * of n_lists lists (aggregatedAttestationPool.ts:320-327 aggregateInto,

@@ -123,19 +123,29 @@ function packRequests(jobs, seed) {
   let nIdx = 0;
   let raw = false;
   let nBits = -1; // bytes of committee bits; -1: no committee set in the call
+  let nRefs = 0; // segments over all committee sets
+  let span = false; // a set over several committees ({committees: [...]}): bls_span_sets
   for (let r = 0; r < nReq; r++) {
     const ss = jobs[r].sets;
     nSets += ss.length;
     for (let i = 0; i < ss.length; i++) {
       const s = ss[i];
-      if (s.type === "committee") nBits = (nBits < 0 ? 0 : nBits) + s.bits.length;
-      else if (s.pubkey !== undefined) raw = true;
+      if (s.type === "committee") {
+        nBits = (nBits < 0 ? 0 : nBits) + s.bits.length;
+        if (s.committees !== undefined) span = true;
+        nRefs += s.committees !== undefined ? s.committees.length : 1;
+      } else if (s.pubkey !== undefined) raw = true;
       else nIdx += s.pubkeyIndices.length;
     }
   }
   if (raw && nBits >= 0) throw Error("mixed raw pubkeys / committee sets in one call");
   // committee sets (bls_committee_sets): the call then goes to addon.verifyCommittees
-  const setCommittee = nBits >= 0 ? new Uint32Array(nSets).fill(SET_NO_COMMITTEE) : null;
+  // ... and with a span among them (bls_span_sets) to addon.verifySpans, every committee set
+  // of the call then being a span, of one segment if it names one committee
+  const setCommittee = nBits >= 0 && !span ? new Uint32Array(nSets).fill(SET_NO_COMMITTEE) : null;
+  const setSpanOff = span ? new Uint32Array(nSets + 1) : null;
+  const spanRefs = span ? new Uint32Array(Math.max(nRefs, 1)) : null;
+  let qr = 0;
   const setBitsOff = nBits >= 0 ? new Uint32Array(nSets + 1) : null;
   const bits = nBits >= 0 ? Buffer.allocUnsafe(Math.max(nBits, 1)) : null;
   let qb = 0;
@@ -171,7 +181,16 @@ function packRequests(jobs, seed) {
         if (s.pubkey.length !== 96) throw Error("raw pubkeys are 96 bytes (uncompressed affine)");
         pubkeys.set(s.pubkey, 96 * k);
       } else if (s.type === "committee") {
-        setCommittee[k] = committeeRef(s.group, s.index);
+        if (span) {
+          const segs = s.committees !== undefined ? s.committees : [s];
+          if (segs.length === 0) throw Error("a span set names at least one committee");
+          for (let t = 0; t < segs.length; t++) {
+            const c = segs[t];
+            spanRefs[qr++] = Array.isArray(c) ? committeeRef(c[0], c[1]) : committeeRef(c.group, c.index);
+          }
+        } else {
+          setCommittee[k] = committeeRef(s.group, s.index);
+        }
         bits.set(s.bits, qb);
         qb += s.bits.length;
         setPkOffsets[k + 1] = q;
@@ -181,18 +200,21 @@ function packRequests(jobs, seed) {
         setPkOffsets[k + 1] = q;
       }
       if (setBitsOff !== null) setBitsOff[k + 1] = qb;
+      if (setSpanOff !== null) setSpanOff[k + 1] = qr;
       k++;
     }
     reqSetOffsets[r + 1] = k;
   }
   return {reqSetOffsets, reqBatchable, messages, signatures, signatureLens: lens, pubkeys, setPkOffsets, pkIndices,
-          setCommittee, setBitsOff, bits, seed: seed || null};
+          setCommittee, setSpanOff, spanRefs, setBitsOff, bits, seed: seed || null};
 }
 
 /** the request of addon.verifySync (bls_gpu_verify): committee sets go through verifySignatureSets */
 function packSync(jobs) {
   const req = packRequests(jobs);
-  if (req.setCommittee !== null) throw Error("committee sets are verified through verifySignatureSets");
+  if (req.setCommittee !== null || req.setSpanOff !== null) {
+    throw Error("committee sets are verified through verifySignatureSets");
+  }
   return req;
 }
 
@@ -213,6 +235,38 @@ function popcountBytes(bits) {
     c += (b + (b >> 4)) & 0x0f;
   }
   return c;
+}
+
+/** set bits of the field at positions [lo, hi) (bit j = bit j & 7 of byte j >> 3) */
+function popcountRange(bits, lo, hi) {
+  let c = 0;
+  for (let j = lo; j < hi && j >> 3 < bits.length; j++) c += (bits[j >> 3] >> (j & 7)) & 1;
+  return c;
+}
+
+/** Pack spans ([{committees: [[group, index] | {group, index}, ...], bits}]) into the arrays
+ * of addon.aggregateSpans (bls_span_sets) */
+function packSpans(spans) {
+  let nRefs = 0;
+  let nBits = 0;
+  for (const s of spans) {
+    nRefs += s.committees.length;
+    nBits += s.bits.length;
+  }
+  const setSpanOff = new Uint32Array(spans.length + 1);
+  const spanRefs = new Uint32Array(Math.max(nRefs, 1));
+  const setBitsOff = new Uint32Array(spans.length + 1);
+  const bits = Buffer.alloc(Math.max(nBits, 1));
+  let qr = 0;
+  let qb = 0;
+  spans.forEach((s, k) => {
+    for (const c of s.committees) spanRefs[qr++] = Array.isArray(c) ? committeeRef(c[0], c[1]) : committeeRef(c.group, c.index);
+    bits.set(s.bits, qb);
+    qb += s.bits.length;
+    setSpanOff[k + 1] = qr;
+    setBitsOff[k + 1] = qb;
+  });
+  return {setSpanOff, spanRefs, setBitsOff, bits};
 }
 
 /** Pack member lists into the arrays of addon.setCommitteeGroup (bls_gpu_set_committee_group) */
@@ -310,6 +364,20 @@ function shardBounds(n, parts) {
 /** Routing weight of a set: 1, or 1 + k / 1024 for an aggregate of k table keys (a G1
  * addition is ~11 of a set's ~12.7k Fp products; lodestar_amd/verifier.py set_weight). */
 function setWeight(s, groups) {
+  if (s.type === "committee" && s.committees !== undefined) {
+    // a span: each segment by itself (bls/committee.hpp span_weight)
+    let k = 0;
+    let at = 0;
+    for (const ref of s.committees) {
+      const [gi, ci] = Array.isArray(ref) ? ref : [ref.group, ref.index];
+      const g = groups !== undefined ? groups.get(gi) : undefined;
+      const n = g !== undefined && g[ci] !== undefined ? g[ci].length : 0;
+      const c = popcountRange(s.bits, at, at + n);
+      k += 1 + Math.min(c, n - c);
+      at += n;
+    }
+    return k > 1 ? 1 + k / AGG_KEY_WEIGHT : 1;
+  }
   if (s.type === "committee") {
     // 1 + min(c, n - c) keys in place of k: the set bits summed directly, or the clear ones
     // taken from the committee's total (bls/committee.hpp committee_weight)
@@ -489,7 +557,9 @@ class GpuBlsVerifier {
    * of every device: `committees` is a list of member lists of validator indices (one
    * epoch's shuffling, or one sync committee).  Sets {type: "committee", group, index, bits,
    * signingRoot, signature} then verify as the aggregate of committee `index`'s members at
-   * the set bits (SSZ order).  Groups belong to a context (bls_gpu_set_committee_group), so
+   * the set bits (SSZ order); with committees: [[group, index], ...] in place of group and
+   * index the set spans those committees, their members concatenated under the one field (an
+   * Electra attestation: bls_gpu_verify_spans).  Groups belong to a context (bls_gpu_set_committee_group), so
    * each context gets its copy, one after another; the first context's validation decides
    * for all, so a rejected registration changes none. */
   async setCommitteeGroup(group, committees) {
@@ -766,6 +836,18 @@ class GpuBlsVerifier {
     this.mainCtx = null;
   }
 
+  /** The aggregate key of each span ({committees: [[group, index], ...], bits}): the members
+   * of its committees, concatenated in order, at the set bits (bls_gpu_aggregate_spans, on
+   * the main-thread context).  Resolves to {keys: [Buffer(96)...], codes: Int32Array}. */
+  async aggregateSpans(spans) {
+    const ctx = this.mainCtx || this.ctxs[0];
+    if (this.closed || ctx === undefined) throw Error("QUEUE_ABORTED");
+    const r = await this._run(ctx, () => this.addon.aggregateSpans(ctx.handle, packSpans(spans)));
+    const keys = [];
+    for (let i = 0; i < spans.length; i++) keys.push(Buffer.from(r.keys.subarray(96 * i, 96 * i + 96)));
+    return {keys, codes: r.codes};
+  }
+
   _settle(verdicts, i) {
     const code = verdicts[i];
     if (code < 0) throw Error(ERROR_MESSAGES[-code] || `BLST_ERROR: ${-code}`);
@@ -776,6 +858,8 @@ class GpuBlsVerifier {
     if (this.closed && this.ctxs.length === 0) throw Error("QUEUE_ABORTED");
     const req = packRequests(jobs);
     // a call holding a committee set is its own kind of message (bls_gpu_verify_committees)
+    // (bls_gpu_verify_spans once one of them spans several committees)
+    if (req.setSpanOff !== null) return this._run(ctx, () => this.addon.verifySpans(ctx.handle, req));
     if (req.setCommittee !== null) return this._run(ctx, () => this.addon.verifyCommittees(ctx.handle, req));
     return this._run(ctx, () => this.addon.verify(ctx.handle, req));
   }
@@ -1135,6 +1219,7 @@ module.exports = {
   shardBounds,
   setWeight,
   packCommittees,
+  packSpans,
   committeeRef,
   SET_NO_COMMITTEE,
   COMMITTEE_GROUPS,

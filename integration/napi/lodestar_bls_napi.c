@@ -252,7 +252,7 @@ static napi_value js_pubkeys_info(napi_env env, napi_callback_info info) {
 }
 
 enum { JOB_VERIFY = 0, JOB_PARTIAL = 1, JOB_FINAL = 2, JOB_SAME_MSG = 3, JOB_DEPOSITS = 4, JOB_COMMITTEES = 5,
-       JOB_SET_GROUP = 6 };
+       JOB_SET_GROUP = 6, JOB_SPANS = 7, JOB_AGG_SPANS = 8 };
 
 typedef struct {
   int kind;
@@ -262,6 +262,9 @@ typedef struct {
   bls_same_msg_batch same;  /* JOB_SAME_MSG */
   bls_deposit_batch dep;    /* JOB_DEPOSITS */
   bls_committee_sets cs;    /* JOB_COMMITTEES (with batch) */
+  bls_span_sets ss;         /* JOB_SPANS (with batch), JOB_AGG_SPANS */
+  uint32_t n_span_sets;     /* JOB_AGG_SPANS */
+  uint8_t* agg_out;         /* JOB_AGG_SPANS: 96 B per set, then the codes in verdicts */
   uint32_t group, n_committees;          /* JOB_SET_GROUP */
   const uint32_t *member_offsets, *members;
   napi_ref keep;          /* the request object: keeps the input buffers alive */
@@ -317,6 +320,10 @@ static void verify_execute(napi_env env, void* data) {
     j->rc = bls_gpu_verify_deposits(j->ctx, &j->dep, j->verdicts, &j->stats);
   else if (j->kind == JOB_COMMITTEES)
     j->rc = bls_gpu_verify_committees(j->ctx, &j->batch, &j->cs, j->verdicts, &j->stats);
+  else if (j->kind == JOB_SPANS)
+    j->rc = bls_gpu_verify_spans(j->ctx, &j->batch, &j->ss, j->verdicts, &j->stats);
+  else if (j->kind == JOB_AGG_SPANS)
+    j->rc = bls_gpu_aggregate_spans(j->ctx, &j->ss, j->n_span_sets, j->agg_out, j->verdicts);
   else if (j->kind == JOB_SET_GROUP)
     j->rc = bls_gpu_set_committee_group(j->ctx, j->group, j->n_committees, j->member_offsets, j->members);
   else
@@ -335,6 +342,8 @@ static void verify_complete(napi_env env, napi_status status, void* data) {
              : j->kind == JOB_SAME_MSG ? "bls_gpu_verify_same_message"
              : j->kind == JOB_DEPOSITS ? "bls_gpu_verify_deposits"
              : j->kind == JOB_COMMITTEES ? "bls_gpu_verify_committees"
+             : j->kind == JOB_SPANS ? "bls_gpu_verify_spans"
+             : j->kind == JOB_AGG_SPANS ? "bls_gpu_aggregate_spans"
              : j->kind == JOB_SET_GROUP ? "bls_gpu_set_committee_group" : "bls_gpu_verify",
              j->rc, (int)status,
              j->rc ? bls_gpu_last_error(j->ctx) : "cancelled");
@@ -373,6 +382,21 @@ static void verify_complete(napi_env env, napi_status status, void* data) {
     napi_value out;
     napi_get_undefined(env, &out);
     napi_resolve_deferred(env, j->deferred, out);
+  } else if (j->kind == JOB_AGG_SPANS) {
+    /* {keys: Uint8Array(96 n), codes: Int32Array(n)} */
+    const size_t n = j->n_span_sets;
+    napi_value out, ab, v;
+    void* dst;
+    napi_create_object(env, &out);
+    napi_create_arraybuffer(env, 96 * (n ? n : 1), &dst, &ab);
+    memcpy(dst, j->agg_out, 96 * n);
+    napi_create_typedarray(env, napi_uint8_array, 96 * n, ab, 0, &v);
+    napi_set_named_property(env, out, "keys", v);
+    napi_create_arraybuffer(env, 4 * (n ? n : 1), &dst, &ab);
+    memcpy(dst, j->verdicts, 4 * n);
+    napi_create_typedarray(env, napi_int32_array, n, ab, 0, &v);
+    napi_set_named_property(env, out, "codes", v);
+    napi_resolve_deferred(env, j->deferred, out);
   } else {
     napi_value ab, out;
     void* dst;
@@ -396,6 +420,7 @@ static void verify_complete(napi_env env, napi_status status, void* data) {
   j->h->inflight -= 1;
   handle_release_if_idle(j->h);
   free(j->verdicts);
+  free(j->agg_out);
   free(j);
 }
 
@@ -512,6 +537,83 @@ static napi_value js_verify_committees(napi_env env, napi_callback_info info) {
   j->cs.set_bits_off = (const uint32_t*)sbo;
   j->cs.bits = (const uint8_t*)bits;
   j->verdicts = (int32_t*)calloc(b.n_reqs ? b.n_reqs : 1, 4);
+  return queue_job(env, h, j, argv[0], argv[1]);
+}
+
+/* The span arrays of a request into a bls_span_sets: setSpanOff (Uint32Array, n_sets + 1),
+ * spanRefs (Uint32Array, one BLS_COMMITTEE_REF per segment), setBitsOff (Uint32Array, n_sets
+ * + 1) and bits (Uint8Array).  Only what the library would read past a buffer's end is
+ * refused here; it checks the offsets themselves and names the set. */
+static int parse_spans(napi_env env, napi_value req, size_t n_sets, bls_span_sets* ss, const char* who) {
+  void *so, *refs, *sbo, *bits;
+  size_t nso, nrefs, nsbo, nbits;
+  char text[160];
+  if (prop(env, req, "setSpanOff", &so, &nso) || prop(env, req, "spanRefs", &refs, &nrefs) ||
+      prop(env, req, "setBitsOff", &sbo, &nsbo) || prop(env, req, "bits", &bits, &nbits) || !so || !sbo) {
+    snprintf(text, sizeof(text), "%s: setSpanOff / spanRefs / setBitsOff / bits missing", who);
+    napi_throw_type_error(env, NULL, text);
+    return -1;
+  }
+  if (nso < 4 * (n_sets + 1) || nsbo < 4 * (n_sets + 1) || nrefs < 4 * (size_t)((const uint32_t*)so)[n_sets] ||
+      nbits < ((const uint32_t*)sbo)[n_sets]) {
+    snprintf(text, sizeof(text), "%s: setSpanOff, spanRefs, setBitsOff or bits is shorter than n_sets and the last "
+                                 "offsets require", who);
+    napi_throw_range_error(env, NULL, text);
+    return -1;
+  }
+  ss->set_span_off = (const uint32_t*)so;
+  ss->span_refs = (const uint32_t*)refs;
+  ss->set_bits_off = (const uint32_t*)sbo;
+  ss->bits = (const uint8_t*)bits;
+  return 0;
+}
+
+/* verifySpans(handle, request) -> Promise<Int32Array>: bls_gpu_verify_spans on a libuv
+ * worker.  The request is verify's (table indices) with the span arrays of parse_spans. */
+static napi_value js_verify_spans(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  bls_handle* h = argc >= 2 ? get_handle(env, argv[0]) : NULL;
+  if (!h) {
+    napi_throw_type_error(env, NULL, "verifySpans(handle, request): no live handle (closed?)");
+    return NULL;
+  }
+  bls_batch b;
+  if (parse_request(env, argv[1], &b)) return NULL;
+  bls_span_sets ss;
+  if (parse_spans(env, argv[1], b.n_sets, &ss, "verifySpans")) return NULL;
+  verify_job* j = (verify_job*)calloc(1, sizeof(verify_job));
+  j->kind = JOB_SPANS;
+  j->batch = b;
+  j->ss = ss;
+  j->verdicts = (int32_t*)calloc(b.n_reqs ? b.n_reqs : 1, 4);
+  return queue_job(env, h, j, argv[0], argv[1]);
+}
+
+/* aggregateSpans(handle, {setSpanOff, spanRefs, setBitsOff, bits}) -> Promise<{keys, codes}>:
+ * bls_gpu_aggregate_spans on a libuv worker; n_sets = setSpanOff.length - 1.  keys holds the
+ * 96-byte uncompressed aggregate of each span, codes its status. */
+static napi_value js_aggregate_spans(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  CHECK(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  bls_handle* h = argc >= 2 ? get_handle(env, argv[0]) : NULL;
+  void* so;
+  size_t nso;
+  if (!h || prop(env, argv[1], "setSpanOff", &so, &nso) || !so || nso < 4) {
+    napi_throw_type_error(env, NULL, "aggregateSpans(handle, {setSpanOff, spanRefs, setBitsOff, bits})");
+    return NULL;
+  }
+  const size_t n = nso / 4 - 1;
+  bls_span_sets ss;
+  if (parse_spans(env, argv[1], n, &ss, "aggregateSpans")) return NULL;
+  verify_job* j = (verify_job*)calloc(1, sizeof(verify_job));
+  j->kind = JOB_AGG_SPANS;
+  j->ss = ss;
+  j->n_span_sets = (uint32_t)n;
+  j->agg_out = (uint8_t*)calloc(n ? n : 1, 96);
+  j->verdicts = (int32_t*)calloc(n ? n : 1, 4);
   return queue_job(env, h, j, argv[0], argv[1]);
 }
 
@@ -816,6 +918,8 @@ static napi_value module_init(napi_env env, napi_value exports) {
       {"verifySameMessage", NULL, js_verify_same_message, NULL, NULL, NULL, napi_default, NULL},
       {"verifyDeposits", NULL, js_verify_deposits, NULL, NULL, NULL, napi_default, NULL},
       {"verifyCommittees", NULL, js_verify_committees, NULL, NULL, NULL, napi_default, NULL},
+      {"verifySpans", NULL, js_verify_spans, NULL, NULL, NULL, napi_default, NULL},
+      {"aggregateSpans", NULL, js_aggregate_spans, NULL, NULL, NULL, napi_default, NULL},
       {"setCommitteeGroup", NULL, js_set_committee_group, NULL, NULL, NULL, napi_default, NULL},
       {"committeeGroupInfo", NULL, js_committee_group_info, NULL, NULL, NULL, napi_default, NULL},
   };

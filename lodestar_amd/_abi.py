@@ -57,6 +57,8 @@ SYMBOLS = (
     "bls_gpu_committee_group_info",
     "bls_gpu_verify_committees",
     "bls_gpu_aggregate_committee_bits",
+    "bls_gpu_verify_spans",
+    "bls_gpu_aggregate_spans",
     "bls_gpu_validate_pubkeys",
     "bls_gpu_partial",
     "bls_gpu_final_check",
@@ -86,6 +88,7 @@ SYMBOLS = (
 COMMITTEE_GROUPS = 8  # BLS_COMMITTEE_GROUPS
 COMMITTEE_MAX_MEMBERS = 131072  # BLS_COMMITTEE_MAX_MEMBERS
 SET_NO_COMMITTEE = 0xFFFFFFFF  # BLS_SET_NO_COMMITTEE
+SPAN_MAX_COMMITTEES = 64  # BLS_SPAN_MAX_COMMITTEES
 
 
 def COMMITTEE_REF(group: int, index: int) -> int:
@@ -224,6 +227,17 @@ class BlsCommitteeSets(ctypes.Structure):
     ]
 
 
+class BlsSpanSets(ctypes.Structure):
+    """bls_span_sets: which sets of a call span several committees, and their fields"""
+
+    _fields_ = [
+        ("set_span_off", ctypes.c_void_p),
+        ("span_refs", ctypes.c_void_p),
+        ("set_bits_off", ctypes.c_void_p),
+        ("bits", ctypes.c_void_p),
+    ]
+
+
 class BlsStats(ctypes.Structure):
     _fields_ = [
         ("batch_retries", ctypes.c_uint32),
@@ -284,6 +298,11 @@ def bind(lib: ctypes.CDLL) -> ctypes.CDLL:
         lib.bls_gpu_verify_committees.restype = i32
         lib.bls_gpu_aggregate_committee_bits.argtypes = [vp, ctypes.POINTER(BlsCommitteeSets), u32, vp, vp]
         lib.bls_gpu_aggregate_committee_bits.restype = i32
+        lib.bls_gpu_verify_spans.argtypes = [vp, ctypes.POINTER(BlsBatch), ctypes.POINTER(BlsSpanSets), vp,
+                                             ctypes.POINTER(BlsStats)]
+        lib.bls_gpu_verify_spans.restype = i32
+        lib.bls_gpu_aggregate_spans.argtypes = [vp, ctypes.POINTER(BlsSpanSets), u32, vp, vp]
+        lib.bls_gpu_aggregate_spans.restype = i32
         lib.bls_gpu_g2_decompress.argtypes = [vp, vp, u32, i32, vp, vp]
         lib.bls_gpu_g2_decompress.restype = i32
         lib.bls_gpu_aggregate_signatures.argtypes = [vp, vp, vp, u32, vp, vp]

@@ -71,7 +71,7 @@ SIMDS = 1024
 
 
 def _resources(remarks: str) -> list[dict]:
-    """Per kernel: name, scratch bytes/lane, occupancy (waves/SIMD) from hipcc's
+    """Per kernel: name, registers, LDS bytes/block, scratch bytes/lane, occupancy (waves/SIMD) from hipcc's
     -Rpass-analysis=kernel-resource-usage remarks."""
     out, cur = [], None
     for line in remarks.splitlines():
@@ -89,6 +89,8 @@ def _resources(remarks: str) -> list[dict]:
             cur["vgprs"] = int(body.split(":", 1)[1].split()[0])
         elif cur is not None and body.startswith("AGPRs:"):
             cur["agprs"] = int(body.split(":", 1)[1].split()[0])
+        elif cur is not None and body.startswith("LDS Size"):
+            cur["lds"] = int(body.split(":", 1)[1].split()[0])
     for k in out:
         k["device_scratch_bytes"] = k.get("scratch", 0) * 64 * k.get("occupancy", 1) * SIMDS
     return out
@@ -214,6 +216,10 @@ def build(jobs: int | None = None, verbose: bool = True, variant: str | None = N
     host_extra = (_variant_flags(variant, host_src.stem) or []) + [f"-DBLS_SCRATCH_PER_QUEUE={per_queue}ull",
                                                                   f'-DBLS_SCRATCH_WORST_KERNEL="{worst}"']
     objs = [_compile(host_src, hdr, verbose, host_extra)] + kobjs
+    if verbose:
+        for k in table:
+            print(f"[build] {k['tu']}: {_plain_name(k['name'])}: {k.get('vgprs', 0)} VGPRs + {k.get('agprs', 0)} AGPRs, "
+                  f"{k.get('lds', 0)} B LDS, {k.get('scratch', 0)} B/lane scratch, {k.get('occupancy')} waves/SIMD", flush=True)
     if not variant:  # every kernel's registers, occupancy and scratch reservation, for the record
         (OUT_DIR / "kernel_resources.json").write_text(json.dumps(
             {"scratch_per_queue": per_queue, "scratch_worst_kernel": worst, "kernels": table}, indent=1))
@@ -333,6 +339,12 @@ def build_committee_host(verbose: bool = True, out: Path | None = None, extra: l
     return _build_host_program("committee_host", (), verbose, out, extra)
 
 
+def build_span_host(verbose: bool = True, out: Path | None = None, extra: list[str] | None = None) -> Path:
+    """The span rules (bls/committee.hpp: a field over several committees) over integer stand-ins
+    for points (tests/native/span_host.cpp), a stand-alone program for tests/; `extra` as above."""
+    return _build_host_program("span_host", (), verbose, out, extra)
+
+
 def build_cpu_baseline(verbose: bool = True) -> Path:
     """The C++ CPU baseline under oracle/cpu (benchmark / test infrastructure, "not
     blst"; oracle/cpu/bls_cpu.cpp), next to its source: bench.py's cpu_baseline leg
@@ -380,4 +392,5 @@ if __name__ == "__main__":
     build_comb_host()
     build_pk_table_host()
     build_committee_host()
+    build_span_host()
     build_cpu_baseline()

@@ -7,6 +7,9 @@
 //               and the host test: the SSZ bit order, the length and padding checks, and
 //               committee_use_complement -- the one place that decides between summing the
 //               members whose bit is set and total - (the members whose bit is clear).
+//               Then the same for a span, one field over several committees
+//               (bls_gpu_verify_spans; k_pk_span): the bit accessor at a bit offset, the
+//               checks over the sum of the sizes, span_weight and span_select_sum.
 //   group       one device allocation: member_offsets (n + 1), members, then one G1J total
 //               per committee, each part 256-byte aligned.  Registered and replaced
 //               wholesale; the slot changes only after the new totals are complete.
@@ -84,6 +87,65 @@ BLS_HD P committee_select_sum(const uint32_t* members, uint32_t n, const uint8_t
   for (uint32_t j = 0; j < n; ++j)
     if (committee_selects(bits, j, comp)) acc = add(acc, at(members[j]));
   return comp ? add(total, neg(acc)) : acc;
+}
+
+// ---- rules of a span: several committees under one field ----------------------------------
+//
+// A span (bls_span_sets, bls_gpu_verify_spans; kernels/k_pk.hip k_pk_span) is the members of
+// its segments -- registered committees, repeats and several groups allowed -- concatenated
+// in order, under one field that runs over the concatenation without a break: segment k of
+// sizes n_0, n_1, ... starts at bit n_0 + ... + n_{k-1}, so every segment after the first
+// may start mid-byte.  This is Electra's Attestation (EIP-7549): committee_bits picks the
+// segments, aggregation_bits is the field.
+
+// bit j of the segment that starts at bit bit_off of the field
+BLS_HD bool span_bit(const uint8_t* bits, uint32_t bit_off, uint32_t j) { return committee_bit(bits, bit_off + j); }
+BLS_HD bool span_selects(const uint8_t* bits, uint32_t bit_off, uint32_t j, bool complement) {
+  return span_bit(bits, bit_off, j) != complement;
+}
+BLS_HD uint32_t span_popcount(const uint8_t* bits, uint32_t bit_off, uint32_t n_members) {
+  uint32_t c = 0;
+  for (uint32_t j = 0; j < n_members; ++j) c += span_bit(bits, bit_off, j) ? 1u : 0u;
+  return c;
+}
+// the members of a span (64 segments of BLS_COMMITTEE_MAX_MEMBERS: 2^23, no wrap)
+BLS_HD uint32_t span_members(const uint32_t* seg_n, uint32_t n_seg) {
+  uint32_t total = 0;
+  for (uint32_t k = 0; k < n_seg; ++k) total += seg_n[k];
+  return total;
+}
+// the length and padding check of a span's field: committee_check_bits over the sum of the
+// segments' sizes (only the last segment's end is followed by padding)
+BLS_HD int32_t span_check_bits(const uint8_t* bits, uint32_t n_bytes, uint32_t total_members) {
+  return committee_check_bits(bits, n_bytes, total_members);
+}
+// keys a span set costs its device: each segment by itself, as committee_weight has it
+BLS_HD uint32_t span_weight(const uint32_t* seg_n, const uint32_t* seg_c, uint32_t n_seg) {
+  uint32_t w = 0;
+  for (uint32_t k = 0; k < n_seg; ++k) w += committee_weight(seg_n[k], seg_c[k]);
+  return w;
+}
+
+// One lane's statement of what k_pk_span computes for a field that passed span_check_bits:
+// the sum over the set bits of the concatenation, each segment taken by itself either
+// directly or as its total minus the members whose bit is clear, by
+// committee_use_complement(n_k, c_k).  seg_members[k] are segment k's n_k = seg_n[k] members
+// and seg_total[k] its total; at / add / neg / zero as in committee_select_sum.
+template <class P, class At, class Add, class Neg>
+BLS_HD P span_select_sum(const uint32_t* const* seg_members, const uint32_t* seg_n, const P* seg_total, uint32_t n_seg,
+                         const uint8_t* bits, const P& zero, bool allow_complement, At at, Add add, Neg neg) {
+  P acc = zero;
+  uint32_t bit_off = 0;
+  for (uint32_t k = 0; k < n_seg; ++k) {
+    const uint32_t n = seg_n[k];
+    const bool comp = allow_complement && committee_use_complement(n, span_popcount(bits, bit_off, n));
+    for (uint32_t j = 0; j < n; ++j)
+      if (span_selects(bits, bit_off, j, comp))
+        acc = add(acc, comp ? neg(at(seg_members[k][j])) : at(seg_members[k][j]));
+    if (comp) acc = add(acc, seg_total[k]);
+    bit_off += n;
+  }
+  return acc;
 }
 
 // ---- a group as the kernels see it -----------------------------------------------------
@@ -178,6 +240,66 @@ static inline int committee_check_sets(const bls_committee_sets* cs, uint32_t n_
   }
   if (cs->set_bits_off[n_sets] && !cs->bits) {
     snprintf(err, err_len, "committee sets: bits missing");
+    return -2;
+  }
+  return 0;
+}
+
+// 0, or -2 with a message naming the set: the arrays of a bls_span_sets against the call's
+// sets.  in_batch: the sets belong to a bls_batch (bls_gpu_verify_spans), which must carry
+// table indices (set_pk_offsets; a raw-key batch is refused) and may mix index-list sets in;
+// otherwise (bls_gpu_aggregate_spans) every set needs at least one segment.
+static inline int span_check_sets(const bls_span_sets* ss, uint32_t n_sets, bool in_batch,
+                                  const uint32_t* set_pk_offsets, char* err, size_t err_len) {
+  if (!ss || (n_sets && (!ss->set_span_off || !ss->set_bits_off))) {
+    snprintf(err, err_len, "span sets: set_span_off or set_bits_off missing");
+    return -2;
+  }
+  if (n_sets == 0) return 0;
+  if (in_batch && !set_pk_offsets) {
+    snprintf(err, err_len, "span sets: the batch must carry table indices (set_pk_offsets), not raw keys");
+    return -2;
+  }
+  if (ss->set_span_off[0] != 0 || ss->set_bits_off[0] != 0) {
+    snprintf(err, err_len, "span sets: %s[0] != 0 (set 0)", ss->set_span_off[0] ? "set_span_off" : "set_bits_off");
+    return -2;
+  }
+  for (uint32_t i = 0; i < n_sets; ++i) {
+    const uint32_t sbeg = ss->set_span_off[i], send = ss->set_span_off[i + 1];
+    const uint32_t beg = ss->set_bits_off[i], end = ss->set_bits_off[i + 1];
+    if (send < sbeg) {
+      snprintf(err, err_len, "span sets: set_span_off not monotone at set %u", i);
+      return -2;
+    }
+    if (end < beg) {
+      snprintf(err, err_len, "span sets: set_bits_off not monotone at set %u", i);
+      return -2;
+    }
+    if (send - sbeg > BLS_SPAN_MAX_COMMITTEES) {
+      snprintf(err, err_len, "span sets: set %u has %u segments, the cap is %u", i, send - sbeg,
+               BLS_SPAN_MAX_COMMITTEES);
+      return -2;
+    }
+    if (send == sbeg) {
+      if (!in_batch) {
+        snprintf(err, err_len, "span sets: set %u has no segment", i);
+        return -2;
+      }
+      if (end != beg) {
+        snprintf(err, err_len, "span sets: set %u has no segment and carries %u bytes of bits", i, end - beg);
+        return -2;
+      }
+    } else if (set_pk_offsets && set_pk_offsets[i + 1] != set_pk_offsets[i]) {
+      snprintf(err, err_len, "span sets: set %u is a span and carries an index list", i);
+      return -2;
+    }
+  }
+  if (ss->set_span_off[n_sets] && !ss->span_refs) {
+    snprintf(err, err_len, "span sets: span_refs missing");
+    return -2;
+  }
+  if (ss->set_bits_off[n_sets] && !ss->bits) {
+    snprintf(err, err_len, "span sets: bits missing");
     return -2;
   }
   return 0;

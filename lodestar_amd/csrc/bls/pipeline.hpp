@@ -68,6 +68,15 @@ struct PipeBufs {
   const uint8_t* bits;
   const uint32_t* bits_sets;
   uint32_t n_bits;
+  // span sets (bls_span_sets; all null / 0: the call has none): set i's segments are the
+  // committees span_refs[set_span_off[i], set_span_off[i + 1]) (an empty range: an index-list
+  // set) under the one field bits[set_bits_off[i], set_bits_off[i + 1]) -- the two arrays
+  // above, which a call fills for its committee sets or for its spans, never both; k_pk_span
+  // sums them one wavefront per set (span_sets: their n_span set indices), stage_pk skips them
+  const uint32_t* set_span_off;
+  const uint32_t* span_refs;
+  const uint32_t* span_sets;
+  uint32_t n_span;
   const uint8_t* msgs;         // n_sets * 32
   const uint8_t* sigs;         // n_sets * 96
   const uint32_t* sig_lens;    // nullable
@@ -214,6 +223,7 @@ BLS_HD void stage_pk(const PipeBufs& b, uint32_t i) {
   int32_t code = BLS_OK;
   G1J acc = jac_infinity<Fp>();
   if (b.set_committee && b.set_committee[i] != BLS_SET_NO_COMMITTEE) return;  // k_pk_bits sums it
+  if (b.set_span_off && b.set_span_off[i + 1] != b.set_span_off[i]) return;   // k_pk_span sums it
   if (b.set_pk_off) {
     uint32_t beg = b.set_pk_off[i], end = b.set_pk_off[i + 1];
     if (b.agg_min && end - beg >= b.agg_min) return;  // k_pk_agg sums it

@@ -1001,6 +1001,8 @@ struct PassArgs {
   const PkView* pk;
   // verify_committees: which sets name a committee, and their bits (nullptr: none does)
   const bls_committee_sets* cs;
+  // verify_spans: which sets are spans of committees, and their fields (nullptr: none is)
+  const bls_span_sets* ss;
 };
 
 // One verify call's pass over the device: shape and plans fixed at construction, buffers
@@ -1045,6 +1047,7 @@ struct VerifyPass {
   uint32_t n_sum = 0;   // requests pairing their own signature sum: iv.reqs[0, n_sum)
   std::vector<int32_t> indiv_verdict;
   std::vector<uint32_t> bits_list;  // the committee sets (k_pk_bits), a.cs
+  std::vector<uint32_t> span_list;  // the span sets (k_pk_span), a.ss
   FoldPlan fold;        // outlive the kernels that read them from the staging area
   GsumPlan indiv_gsum;
 
@@ -1061,6 +1064,9 @@ struct VerifyPass {
     if (a.cs)
       for (uint32_t i = 0; i < sh.n; ++i)
         if (a.cs->set_committee[i] != BLS_SET_NO_COMMITTEE) bits_list.push_back(i);
+    if (a.ss)
+      for (uint32_t i = 0; i < sh.n; ++i)
+        if (a.ss->set_span_off[i + 1] != a.ss->set_span_off[i]) span_list.push_back(i);
   }
 
   // ---- workspace: inputs first (they live in the mapped staging area), then intermediates.
@@ -1081,6 +1087,13 @@ struct VerifyPass {
       b.set_bits_off = c.take<uint32_t>(n + 1);
       b.bits = c.take<uint8_t>(a.cs->set_bits_off[n]);
       b.bits_sets = c.take<uint32_t>(bits_list.size());
+    }
+    if (!span_list.empty()) {
+      b.set_span_off = c.take<uint32_t>(n + 1);
+      b.span_refs = c.take<uint32_t>(a.ss->set_span_off[n]);
+      b.set_bits_off = c.take<uint32_t>(n + 1);
+      b.bits = c.take<uint8_t>(a.ss->set_bits_off[n]);
+      b.span_sets = c.take<uint32_t>(span_list.size());
     }
     b.msgs = sh.dep ? nullptr : c.take<uint8_t>(32ull * n);  // (a deposit call: device memory, below)
     if (sh.dep) {
@@ -1194,6 +1207,10 @@ struct VerifyPass {
       b.cm_groups = ctx->cm_dev;
       b.n_bits = (uint32_t)bits_list.size();
     }
+    if (!span_list.empty()) {
+      b.cm_groups = ctx->cm_dev;
+      b.n_span = (uint32_t)span_list.size();
+    }
   }
 
   template <class T>
@@ -1221,6 +1238,7 @@ struct VerifyPass {
     stage_vec(b.chunk_reqs, plan.chunk_reqs);
     if (!pl.agg_list.empty()) stage_vec(b.agg_sets, pl.agg_list);
     if (!bits_list.empty()) stage_vec(b.bits_sets, bits_list);
+    if (!span_list.empty()) stage_vec(b.span_sets, span_list);
     if (sh.dedup) {
       stage_vec(b.msg_uniq, pl.msg_uniq);
       stage_vec(b.msg_rep, pl.msg_rep);
@@ -1240,6 +1258,12 @@ struct VerifyPass {
       stage_copy(ctx, b.set_committee, a.cs->set_committee, sizeof(uint32_t) * n);
       stage_copy(ctx, b.set_bits_off, a.cs->set_bits_off, sizeof(uint32_t) * (n + 1));
       stage_copy(ctx, b.bits, a.cs->bits, a.cs->set_bits_off[n]);
+    }
+    if (!span_list.empty()) {
+      stage_copy(ctx, b.set_span_off, a.ss->set_span_off, sizeof(uint32_t) * (n + 1));
+      stage_copy(ctx, b.span_refs, a.ss->span_refs, sizeof(uint32_t) * a.ss->set_span_off[n]);
+      stage_copy(ctx, b.set_bits_off, a.ss->set_bits_off, sizeof(uint32_t) * (n + 1));
+      stage_copy(ctx, b.bits, a.ss->bits, a.ss->set_bits_off[n]);
     }
     if (sh.dep) {
       stage_copy(ctx, dep.pubkeys48, a.dep->pubkeys48, 48ull * n);
@@ -1328,7 +1352,8 @@ struct VerifyPass {
     } else {
       HIPC(ctx, launch_k_pk(b, s));
       HIPC(ctx, launch_k_pk_agg(b, s));
-      HIPC(ctx, launch_k_pk_bits(b, s)); dbg_sync(s, "k_pk");
+      HIPC(ctx, launch_k_pk_bits(b, s));
+      HIPC(ctx, launch_k_pk_span(b, s)); dbg_sync(s, "k_pk");
     }
     ctx->first_bad_slot ^= 1u;
     HIPC(ctx, hipEventRecord(ctx->ev[1], s));
@@ -1881,7 +1906,7 @@ static int verify_impl(bls_gpu_ctx* ctx, const bls_batch* in, int32_t* verdicts,
                        uint32_t scalar_base, uint8_t* partial_out, int32_t* partial_status,
                        uint32_t* partial_err = nullptr, const std::vector<uint32_t>* req_bounds = nullptr,
                        const SameMsgPlan* sm = nullptr, const bls_deposit_batch* dep = nullptr,
-                       const bls_committee_sets* cs = nullptr) {
+                       const bls_committee_sets* cs = nullptr, const bls_span_sets* ss = nullptr) {
   CTX_LOCK(ctx);
   ctx->wait_block = wait_blocks(knobs(), in->n_sets);
   // the table as this call sees it: kept until the stream is idle (every stage of a pass
@@ -1890,7 +1915,7 @@ static int verify_impl(bls_gpu_ctx* ctx, const bls_batch* in, int32_t* verdicts,
   PkView pk;
   if (!dep) pk = pk_snapshot(ctx);
   const int rc = verify_body(ctx, in, PassArgs{verdicts, stats, scalar_base, partial_out, partial_status, partial_err,
-                                               req_bounds, sm, dep, dep ? nullptr : &pk, cs});
+                                               req_bounds, sm, dep, dep ? nullptr : &pk, cs, ss});
   if (rc != 0) (void)hipStreamSynchronize(ctx->stream);
   if (rc < 0 && ctx->msm_state) {
     (void)hipMemsetAsync(ctx->msm_state, 0, sizeof(uint32_t) * MSM_STATE_WORDS, ctx->stream);
@@ -1917,6 +1942,16 @@ int bls_gpu_verify_committees(bls_gpu_ctx* ctx, const bls_batch* in, const bls_c
     if (const int rc = committee_check_sets(cs, in->n_sets, in->set_pk_offsets, ctx->err, sizeof(ctx->err))) return rc;
   }
   return verify_impl(ctx, in, verdicts, stats, 0u, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, cs);
+}
+
+int bls_gpu_verify_spans(bls_gpu_ctx* ctx, const bls_batch* in, const bls_span_sets* ss, int32_t* verdicts,
+                         bls_stats* stats) {
+  if (!ctx || !in) return -2;
+  {
+    CTX_LOCK(ctx);  // (for ctx->err; verify_impl takes the lock for the call itself)
+    if (const int rc = span_check_sets(ss, in->n_sets, true, in->set_pk_offsets, ctx->err, sizeof(ctx->err))) return rc;
+  }
+  return verify_impl(ctx, in, verdicts, stats, 0u, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, ss);
 }
 
 int bls_gpu_verify_many(bls_gpu_ctx* ctx, const bls_batch* batches, uint32_t n_batches, int32_t* verdicts,
@@ -2211,6 +2246,69 @@ int bls_gpu_aggregate_committee_bits(bls_gpu_ctx* ctx, const bls_committee_sets*
   if (n_bytes) HIPC(ctx, hipMemcpyAsync((void*)b.bits, cs->bits, n_bytes, hipMemcpyHostToDevice, s));
   HIPC(ctx, hipMemcpyAsync((void*)b.bits_sets, all.data(), sizeof(uint32_t) * n_sets, hipMemcpyHostToDevice, s));
   HIPC(ctx, launch_k_pk_bits(b, s));
+  HIPC(ctx, launch_k_aggregate(b, d_out, s));  // stage_pk skips every set; it serializes them
+  HIPC(ctx, hipMemcpyAsync(out96, d_out, 96ull * n_sets, hipMemcpyDeviceToHost, s));
+  if (codes) HIPC(ctx, hipMemcpyAsync(codes, b.pk_status, sizeof(int32_t) * n_sets, hipMemcpyDeviceToHost, s));
+  HIPC(ctx, hipStreamSynchronize(s));
+  drain.armed = false;
+  return 0;
+}
+
+int bls_gpu_aggregate_spans(bls_gpu_ctx* ctx, const bls_span_sets* ss, uint32_t n_sets, uint8_t* out96,
+                            int32_t* codes) {
+  if (!ctx) return -2;
+  CTX_LOCK(ctx);
+  if (const int rc = span_check_sets(ss, n_sets, false, nullptr, ctx->err, sizeof(ctx->err))) return rc;
+  if (n_sets && !out96) {
+    snprintf(ctx->err, sizeof(ctx->err), "span sets: out96 missing");
+    return -2;
+  }
+  HIPC(ctx, hipSetDevice(ctx->device));
+  if (n_sets == 0) return 0;
+  const uint32_t n_refs = ss->set_span_off[n_sets], n_bytes = ss->set_bits_off[n_sets];
+  PipeBufs b;
+  memset(&b, 0, sizeof(b));
+  auto carve = [&](Carver& c, uint8_t*& d_out) {
+    b.set_span_off = c.take<uint32_t>(n_sets + 1);
+    b.span_refs = c.take<uint32_t>(n_refs);
+    b.set_bits_off = c.take<uint32_t>(n_sets + 1);
+    b.bits = c.take<uint8_t>(n_bytes);
+    b.span_sets = c.take<uint32_t>(n_sets);
+    b.pk = c.take<G1J>(n_sets);
+    b.pk_status = c.take<int32_t>(n_sets);
+    d_out = c.take<uint8_t>(96ull * n_sets);
+  };
+  uint8_t* d_out = nullptr;
+  {
+    Carver c{nullptr, 0};
+    carve(c, d_out);
+    if (ensure_dev(ctx, c.off)) return -1;
+  }
+  Carver c{ctx->dev_ws, 0};
+  carve(c, d_out);
+  b.n_sets = b.n_span = n_sets;
+  b.cm_groups = ctx->cm_dev;
+  const PkView pk = pk_snapshot(ctx);  // dropped at return; an error path waits first (below)
+  b.pk_table = pk.table();
+  b.pk_table_n = pk.snap.n;
+  std::vector<uint32_t> all(n_sets);
+  for (uint32_t i = 0; i < n_sets; ++i) all[i] = i;
+  hipStream_t s = ctx->stream;
+  struct Drain {  // a failed copy or launch leaves earlier kernels on the stream
+    hipStream_t s;
+    bool armed;
+    ~Drain() {
+      if (armed) (void)hipStreamSynchronize(s);
+    }
+  } drain{s, true};
+  HIPC(ctx, hipMemcpyAsync((void*)b.set_span_off, ss->set_span_off, sizeof(uint32_t) * (n_sets + 1),
+                           hipMemcpyHostToDevice, s));
+  HIPC(ctx, hipMemcpyAsync((void*)b.span_refs, ss->span_refs, sizeof(uint32_t) * n_refs, hipMemcpyHostToDevice, s));
+  HIPC(ctx, hipMemcpyAsync((void*)b.set_bits_off, ss->set_bits_off, sizeof(uint32_t) * (n_sets + 1),
+                           hipMemcpyHostToDevice, s));
+  if (n_bytes) HIPC(ctx, hipMemcpyAsync((void*)b.bits, ss->bits, n_bytes, hipMemcpyHostToDevice, s));
+  HIPC(ctx, hipMemcpyAsync((void*)b.span_sets, all.data(), sizeof(uint32_t) * n_sets, hipMemcpyHostToDevice, s));
+  HIPC(ctx, launch_k_pk_span(b, s));
   HIPC(ctx, launch_k_aggregate(b, d_out, s));  // stage_pk skips every set; it serializes them
   HIPC(ctx, hipMemcpyAsync(out96, d_out, 96ull * n_sets, hipMemcpyDeviceToHost, s));
   if (codes) HIPC(ctx, hipMemcpyAsync(codes, b.pk_status, sizeof(int32_t) * n_sets, hipMemcpyDeviceToHost, s));

@@ -1,5 +1,6 @@
 // Pubkey stage: deserialize raw 96-byte keys or sum device-table keys (aggregate sets given
-// as index lists, or as a registered committee and its participation bits), plus the
+// as index lists, as a registered committee and its participation bits, or as a span of
+// committees under one field), plus the
 // pubkey-table loader and the per-request status pass (small kernels).
 #include "../launchers.hpp"
 
@@ -161,6 +162,167 @@ __global__ __launch_bounds__(BLS_BLOCK) void k_pk_bits(PipeBufs b) {
 hipError_t launch_k_pk_bits(const PipeBufs& b, hipStream_t s) {
   if (b.n_bits == 0) return hipSuccess;
   k_pk_bits<<<b.n_bits, BLS_BLOCK, 0, s>>>(b);
+  return hipGetLastError();
+}
+
+// A span set (b.span_sets; bls_gpu_verify_spans) = the aggregate set whose index list is the
+// members of its segments, concatenated, at the set bits of one field (bls/committee.hpp
+// span_select_sum): one wavefront per set.
+//   segments   lane k resolves segment k (at most BLS_SPAN_MAX_COMMITTEES = 64 = one lane
+//              each): its group, its member range, its first bit (a prefix sum over LDS).
+//   counts     c_k by k_pk_bits' ballot loop at the segment's bit offset;
+//              committee_use_complement(n_k, c_k) segment by segment, kept as one 64-bit mask.
+//   selection  a mainnet set is 64 segments of ~500 members, nearly all complemented with a
+//              handful of clear bits each, so the selected positions of ALL segments go
+//              through one compaction ring (committee_wave_sum's, an entry carrying its sign
+//              as well: a complemented segment's clear-bit members are subtracted, the affine
+//              point with y negated) that the lanes drain 64 at a time across segment
+//              boundaries: at most ceil(S / 64) mixed additions per lane, S = sum_k min(c_k,
+//              n_k - c_k), not one under-filled drain and one tree per segment.
+//   totals     lane k takes the total of segment k if it is complemented, as the upper half
+//              of the tree's input; the one tree then starts a level higher (128 entries).
+// Every loop bound is uniform over the wavefront.  The group law's edges are jac_add's and
+// jac_add_aff's: a committee repeated (P + P), a key taken once directly and once through a
+// complement (P + (-P)), a total at infinity.
+__global__ __launch_bounds__(BLS_BLOCK) void k_pk_span(PipeBufs b) {
+  __shared__ G1J part[2 * BLS_BLOCK];
+  __shared__ uint32_t ring[2 * BLS_BLOCK];
+  __shared__ uint8_t ring_neg[2 * BLS_BLOCK];
+  __shared__ uint32_t seg_n[BLS_BLOCK], seg_bit[BLS_BLOCK];
+  __shared__ const uint32_t* seg_mem[BLS_BLOCK];
+  const uint32_t lane = threadIdx.x;
+  const uint32_t i = b.span_sets[blockIdx.x];
+  const uint32_t sbeg = b.set_span_off[i];
+  const uint32_t n_seg = b.set_span_off[i + 1] - sbeg;  // 1..64 (span_check_sets)
+  int32_t code = BLS_OK;
+
+  // ---- segments
+  const G1J* my_total = nullptr;
+  uint32_t my_n = 0;
+  bool bad = false;
+  if (lane < n_seg) {
+    const uint32_t ref = b.span_refs[sbeg + lane];
+    const uint32_t g = committee_ref_group(ref), ci = committee_ref_index(ref);
+    if (g >= BLS_COMMITTEE_GROUPS || !b.cm_groups[g].offsets || ci >= b.cm_groups[g].n) {
+      bad = true;  // an unregistered group, an index past the group
+    } else {
+      const CommitteeGroupDev grp = b.cm_groups[g];
+      const uint32_t beg = grp.offsets[ci];
+      my_n = grp.offsets[ci + 1] - beg;
+      seg_mem[lane] = grp.members + beg;
+      my_total = static_cast<const G1J*>(grp.totals) + ci;
+    }
+  }
+  seg_n[lane] = my_n;
+  __syncthreads();
+  uint32_t my_bit = 0, total_n = 0;
+  for (uint32_t k = 0; k < n_seg; ++k) {
+    const uint32_t nk = seg_n[k];
+    if (k < lane) my_bit += nk;
+    total_n += nk;
+  }
+  seg_bit[lane] = my_bit;
+  __syncthreads();
+  if (__any(bad)) code = BLS_BAD_ENCODING;
+
+  const uint32_t boff = b.set_bits_off[i];
+  const uint8_t* bits = b.bits + boff;
+  if (code == BLS_OK) code = span_check_bits(bits, b.set_bits_off[i + 1] - boff, total_n);
+
+  G1J acc = jac_infinity<Fp>();
+  G1J tot = jac_infinity<Fp>();
+  if (code == BLS_OK) {
+    // ---- counts
+    uint64_t comp_mask = 0;
+    uint32_t c_all = 0;
+    for (uint32_t k = 0; k < n_seg; ++k) {
+      const uint32_t n = seg_n[k], off = seg_bit[k];
+      uint32_t c = 0;
+      for (uint32_t base = 0; base < n; base += BLS_BLOCK) {
+        const uint32_t j = base + lane;
+        c += __popcll(__ballot(j < n && span_bit(bits, off, j)));
+      }
+      c_all += c;
+      if (committee_use_complement(n, c)) comp_mask |= 1ull << k;
+    }
+    if (c_all == 0) {
+      code = BLS_EMPTY_AGGREGATE;
+    } else {
+      // ---- selection: one ring over all segments
+      uint32_t pending = 0;
+      bool past = false;  // a member at or past the table (registration rules it out)
+      for (uint32_t k = 0; k < n_seg; ++k) {
+        const uint32_t n = seg_n[k], off = seg_bit[k];
+        const uint32_t* mem = seg_mem[k];
+        const bool comp = (comp_mask >> k) & 1ull;
+        for (uint32_t base = 0; base < n; base += BLS_BLOCK) {
+          const uint32_t j = base + lane;
+          const bool sel = j < n && span_selects(bits, off, j, comp);
+          const uint64_t mask = __ballot(sel);
+          if (sel) {
+            const uint32_t at = pending + __popcll(mask & ((1ull << lane) - 1ull));
+            ring[at] = mem[j];
+            ring_neg[at] = comp ? 1 : 0;
+          }
+          pending += __popcll(mask);  // <= 63 + 64: the ring holds 128
+          __syncthreads();
+          if (pending >= BLS_BLOCK) {
+            const uint32_t idx = ring[lane];
+            const bool neg = ring_neg[lane] != 0;
+            const uint32_t rest = pending - BLS_BLOCK;
+            const uint32_t carry = lane < rest ? ring[BLS_BLOCK + lane] : 0u;
+            const uint8_t carry_neg = lane < rest ? ring_neg[BLS_BLOCK + lane] : (uint8_t)0;
+            __syncthreads();
+            if (lane < rest) {
+              ring[lane] = carry;
+              ring_neg[lane] = carry_neg;
+            }
+            pending = rest;
+            if (idx >= b.pk_table_n) {
+              past = true;
+            } else {
+              G1A q = b.pk_table[idx];
+              if (neg) q.y = fp_neg(q.y);
+              acc = jac_add_aff(acc, q);
+            }
+            __syncthreads();
+          }
+        }
+      }
+      if (lane < pending) {
+        const uint32_t idx = ring[lane];
+        if (idx >= b.pk_table_n) {
+          past = true;
+        } else {
+          G1A q = b.pk_table[idx];
+          if (ring_neg[lane]) q.y = fp_neg(q.y);
+          acc = jac_add_aff(acc, q);
+        }
+      }
+      if (__any(past)) code = BLS_BAD_ENCODING;
+      // ---- totals
+      if (lane < n_seg && ((comp_mask >> lane) & 1ull)) tot = *my_total;
+    }
+  }
+  // ---- one tree over the lanes' sums and the complemented segments' totals
+  part[lane] = acc;
+  part[BLS_BLOCK + lane] = tot;
+  __syncthreads();
+  for (uint32_t s = BLS_BLOCK; s >= 1; s >>= 1) {
+    if (lane < s) part[lane] = jac_add(part[lane], part[lane + s]);
+    __syncthreads();
+  }
+  if (lane == 0) {
+    const G1J sum = code == BLS_OK ? part[0] : jac_infinity<Fp>();
+    b.pk[i] = sum;
+    b.pk_status[i] = code;
+    if (b.pk_inf) b.pk_inf[i] = (code == BLS_OK && jac_is_inf(sum)) ? 1 : 0;
+  }
+}
+
+hipError_t launch_k_pk_span(const PipeBufs& b, hipStream_t s) {
+  if (b.n_span == 0) return hipSuccess;
+  k_pk_span<<<b.n_span, BLS_BLOCK, 0, s>>>(b);
   return hipGetLastError();
 }
 

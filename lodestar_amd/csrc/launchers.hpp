@@ -21,6 +21,7 @@ hipError_t launch_k_pk(const bls::PipeBufs& b, hipStream_t s);
 hipError_t launch_k_pk_agg(const bls::PipeBufs& b, hipStream_t s);
 // committee sets (bls/committee.hpp): b.bits_sets' sums, and a group's totals at registration
 hipError_t launch_k_pk_bits(const bls::PipeBufs& b, hipStream_t s);
+hipError_t launch_k_pk_span(const bls::PipeBufs& b, hipStream_t s);  // b.span_sets' sums
 hipError_t launch_k_committee_totals(const bls::CommitteeGroupDev& grp, bls::G1J* totals, const bls::G1A* table,
                                      uint32_t table_n, hipStream_t s);
 hipError_t launch_k_aggregate(const bls::PipeBufs& b, uint8_t* out96, hipStream_t s);

@@ -13,7 +13,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from ._abi import (COMMITTEE_REF, ERR_ADMISSION, SET_NO_COMMITTEE, BlsAdmission, BlsBatch, BlsCommitteeInfo,
-                   BlsCommitteeSets, BlsDepositBatch, BlsSameMsgBatch, BlsStats, load_library)
+                   BlsCommitteeSets, BlsDepositBatch, BlsSameMsgBatch, BlsSpanSets, BlsStats, load_library)
 
 
 def _ptr(a: np.ndarray | None):
@@ -105,6 +105,10 @@ class PackedBatch:
     set_committee: np.ndarray | None = None  # uint32[n_sets]: COMMITTEE_REF or SET_NO_COMMITTEE
     set_bits_off: np.ndarray | None = None  # uint32[n_sets + 1] byte offsets into bits
     bits: np.ndarray | None = None  # uint8[...]
+    # span sets (bls_span_sets; None: the batch has none).  A batch holds committee sets or
+    # span sets, never both: with a span in it, its committee sets are one-segment spans
+    set_span_off: np.ndarray | None = None  # uint32[n_sets + 1] into span_refs
+    span_refs: np.ndarray | None = None  # uint32[...]: COMMITTEE_REF per segment
     # the bls_batch view of these arrays, built on first use (GpuContext._batch_struct):
     # a pass of 64 calls re-packed its 64 structs under the GIL at every submission
     _cstruct: object = field(default=None, repr=False, compare=False)
@@ -128,25 +132,42 @@ def pack_requests(requests, seed: bytes | None = None) -> PackedBatch:
     A set may also be a dict {"committee": (group, index), "bits": bytes, "message": msg32,
     "signature": sig}: the aggregate of a registered committee's members at the set bits
     (GpuContext.set_committee_group).  Such sets mix with index-list sets, not with raw
-    keys, and the batch then goes through GpuContext.verify_committees_packed."""
+    keys, and the batch then goes through GpuContext.verify_committees_packed.
+
+    Or a dict {"committees": [(group, index), ...], "bits": bytes, "message": msg32,
+    "signature": sig}: a span, the members of those committees concatenated in order under
+    one field (an Electra attestation's committee_bits and aggregation_bits).  In a batch that
+    holds any such dict a {"committee": ...} dict becomes a one-segment span, and the batch
+    goes through GpuContext.verify_spans_packed."""
     offs = [0]
     batchable = []
     msgs, sigs, lens = [], [], []
     raw_pks, idx_offs, idx = [], [0], []
     table_mode = None
     refs, bits_offs, bits = [], [0], []
+    span_offs, span_refs, any_span = [0], [], False
     for is_b, sets in requests:
         batchable.append(1 if is_b else 0)
         for one in sets:
             if isinstance(one, dict):
-                group, index = one["committee"]
                 pk, msg, sig = (), one["message"], one["signature"]
-                refs.append(COMMITTEE_REF(int(group), int(index)))
+                if "committees" in one:
+                    any_span = True
+                    segs = [COMMITTEE_REF(int(g), int(i)) for g, i in one["committees"]]
+                    if not segs:
+                        raise ValueError("a span set names at least one committee")
+                    span_refs.extend(segs)
+                    refs.append(segs[0])  # (marks the set; a batch with a span ships span_refs, not refs)
+                else:
+                    group, index = one["committee"]
+                    refs.append(COMMITTEE_REF(int(group), int(index)))
+                    span_refs.append(refs[-1])
                 bits.append(bytes(one["bits"]))
             else:
                 pk, msg, sig = one
                 refs.append(SET_NO_COMMITTEE)
                 bits.append(b"")
+            span_offs.append(len(span_refs))
             bits_offs.append(bits_offs[-1] + len(bits[-1]))
             this_table = not isinstance(pk, (bytes, bytearray, memoryview, np.ndarray))
             if table_mode is None:
@@ -184,7 +205,11 @@ def pack_requests(requests, seed: bytes | None = None) -> PackedBatch:
         pb.set_pk_offsets = np.array(idx_offs, dtype=np.uint32)
         pb.pk_indices = np.array(idx if idx else [0], dtype=np.uint32)
         if any(r != SET_NO_COMMITTEE for r in refs):
-            pb.set_committee = np.array(refs, dtype=np.uint32)
+            if any_span:
+                pb.set_span_off = np.array(span_offs, dtype=np.uint32)
+                pb.span_refs = np.array(span_refs, dtype=np.uint32)
+            else:
+                pb.set_committee = np.array(refs, dtype=np.uint32)
             pb.set_bits_off = np.array(bits_offs, dtype=np.uint32)
             pb.bits = np.frombuffer(b"".join(bits) or b"\0", dtype=np.uint8).copy()
     else:
@@ -440,6 +465,50 @@ class GpuContext:
         codes = np.zeros(max(n, 1), dtype=np.int32)
         rc = self.lib.bls_gpu_aggregate_committee_bits(self._h, ctypes.byref(cs), n, _ptr(out), _ptr(codes))
         self._check(rc, "bls_gpu_aggregate_committee_bits")
+        raw = out.tobytes()
+        return [raw[96 * i: 96 * i + 96] for i in range(n)], codes[:n]
+
+    # -- spans: sets over several committees under one field ------------------------
+    @staticmethod
+    def _span_struct(set_span_off, span_refs, set_bits_off, bits):
+        keep = [np.ascontiguousarray(set_span_off, dtype=np.uint32), np.ascontiguousarray(span_refs, dtype=np.uint32),
+                np.ascontiguousarray(set_bits_off, dtype=np.uint32), np.ascontiguousarray(bits, dtype=np.uint8)]
+        ss = BlsSpanSets()
+        ss.set_span_off, ss.span_refs, ss.set_bits_off, ss.bits = (_ptr(a) for a in keep)
+        return ss, keep
+
+    def verify_spans_packed(self, pb: PackedBatch) -> tuple[np.ndarray, BlsStats]:
+        """bls_gpu_verify_spans for a batch packed from requests that hold span sets
+        (pack_requests); one without any goes where verify_committees_packed sends it."""
+        if pb.set_span_off is None:
+            return self.verify_committees_packed(pb)
+        b, _keep = self._batch_struct(pb)
+        ss, _keep2 = self._span_struct(pb.set_span_off, pb.span_refs, pb.set_bits_off, pb.bits)
+        verdicts = np.zeros(max(pb.n_reqs, 1), dtype=np.int32)
+        stats = BlsStats()
+        rc = self.lib.bls_gpu_verify_spans(self._h, ctypes.byref(b), ctypes.byref(ss), _ptr(verdicts),
+                                           ctypes.byref(stats))
+        self._check(rc, "bls_gpu_verify_spans")
+        return verdicts[: pb.n_reqs], stats
+
+    def aggregate_spans(self, sets) -> tuple[list[bytes], np.ndarray]:
+        """sets: list of ([(group, index), ...], bits).  The aggregate key of each span -- the
+        members of its committees concatenated in order, at the set bits -- as aggregate_pubkeys
+        gives it for the expanded index list: 96-byte uncompressed keys and codes
+        (bls_gpu_aggregate_spans)."""
+        n = len(sets)
+        refs, soffs, boffs = [], [0], [0]
+        for segs, bt in sets:
+            refs.extend(COMMITTEE_REF(int(g), int(i)) for g, i in segs)
+            soffs.append(len(refs))
+            boffs.append(boffs[-1] + len(bytes(bt)))
+        ss, _keep = self._span_struct(np.array(soffs, dtype=np.uint32), np.array(refs if refs else [0], dtype=np.uint32),
+                                      np.array(boffs, dtype=np.uint32),
+                                      np.frombuffer(b"".join(bytes(bt) for _, bt in sets) or b"\0", dtype=np.uint8))
+        out = np.zeros(96 * max(n, 1), dtype=np.uint8)
+        codes = np.zeros(max(n, 1), dtype=np.int32)
+        rc = self.lib.bls_gpu_aggregate_spans(self._h, ctypes.byref(ss), n, _ptr(out), _ptr(codes))
+        self._check(rc, "bls_gpu_aggregate_spans")
         raw = out.tobytes()
         return [raw[96 * i: 96 * i + 96] for i in range(n)], codes[:n]
 

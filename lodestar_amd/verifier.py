@@ -78,6 +78,9 @@ a group registered with `set_committee_group` -- which reaches every context of 
 device and those opened later (`add_context`) -- and its participation bits.  A job
 holding one goes out as its own bls_gpu_verify_committees message and weighs
 1 + min(c, n - c) keys per such set; split calls and same-message calls keep index lists.
+`SpanSet(refs, bits, signing_root, signature)` is the same over several committees under one
+field (an Electra attestation): it goes out in a bls_gpu_verify_spans message and weighs the
+sum of its segments' weights (bls/committee.hpp span_weight).
 """
 from __future__ import annotations
 
@@ -123,6 +126,21 @@ class CommitteeSet:
 
     group: int
     index: int
+    bits: bytes
+    signing_root: bytes
+    signature: bytes
+
+
+@dataclass
+class SpanSet:
+    """An aggregate set over several committees (EIP-7549): `refs` lists (group, index) of
+    registered committees in order -- what Attestation.committee_bits selects -- and `bits` is
+    one field over their members concatenated (aggregation_bits, SSZ order, no delimiter), so
+    a committee after the first may start mid-byte.  It verifies exactly as the SignatureSet
+    whose pubkey lists those members at the set bits; a committee may repeat, and a key in
+    several of them counts each time."""
+
+    refs: Sequence
     bits: bytes
     signing_root: bytes
     signature: bytes
@@ -193,7 +211,21 @@ def committee_weight_keys(n_members: int, n_set: int) -> int:
     return 1 + min(n_set, max(n_members - n_set, 0))
 
 
+def span_weight_keys(seg_n, seg_c) -> int:
+    """Keys a span set costs its device (bls/committee.hpp span_weight): each segment by itself"""
+    return sum(committee_weight_keys(n, c) for n, c in zip(seg_n, seg_c))
+
+
+def _bits_between(bits: bytes, lo: int, hi: int) -> int:
+    """set bits of the field at positions [lo, hi) (bit j = bit j & 7 of byte j >> 3)"""
+    v = int.from_bytes(bits, "little")
+    return bin((v >> lo) & ((1 << max(hi - lo, 0)) - 1)).count("1")
+
+
 def _wire(s):
+    if isinstance(s, SpanSet):
+        return {"committees": [(int(g), int(i)) for g, i in s.refs], "bits": bytes(s.bits),
+                "message": bytes(s.signing_root), "signature": bytes(s.signature)}
     if isinstance(s, CommitteeSet):
         return {"committee": (int(s.group), int(s.index)), "bits": bytes(s.bits), "message": bytes(s.signing_root),
                 "signature": bytes(s.signature)}
@@ -372,6 +404,16 @@ class GpuBlsVerifier:
         """set_weight of a wire set; a committee set weighs 1 + min(c, n - c) keys in place of k"""
         if not isinstance(wire, dict):
             return set_weight(wire[0])
+        if "committees" in wire:
+            seg_n, seg_c, at = [], [], 0
+            for group, index in wire["committees"]:
+                members = self._groups.get(group)
+                n = len(members[index]) if members is not None and 0 <= index < len(members) else 0
+                seg_n.append(n)
+                seg_c.append(_bits_between(wire["bits"], at, at + n))
+                at += n
+            k = span_weight_keys(seg_n, seg_c)
+            return 1.0 + (k / AGG_KEY_WEIGHT if k > 1 else 0.0)
         group, index = wire["committee"]
         members = self._groups.get(group)
         c = _popcount(wire["bits"])
@@ -388,8 +430,8 @@ class GpuBlsVerifier:
                                     verify_on_main_thread: bool = False) -> Future:
         # pubkeys are aggregated (on the device) whichever branch runs (index.ts:136)
         self.metrics.bls.aggregatedPubkeys.inc(
-            get_aggregated_pubkeys_count([s for s in sets if not isinstance(s, CommitteeSet)])
-            + sum(_popcount(bytes(s.bits)) for s in sets if isinstance(s, CommitteeSet)))
+            get_aggregated_pubkeys_count([s for s in sets if not isinstance(s, (CommitteeSet, SpanSet))])
+            + sum(_popcount(bytes(s.bits)) for s in sets if isinstance(s, (CommitteeSet, SpanSet))))
         if verify_on_main_thread and not self.verify_all_multi_thread:
             fut: Future = Future()
             stop = self.metrics.blsThreadPool.mainThreadDurationInThreadPool.start_timer()
@@ -404,7 +446,7 @@ class GpuBlsVerifier:
         sets = list(sets)
         # (a sharded call keeps index lists, as bls_gpu_partial does)
         if (not batchable and len(self.devices) > 1 and len(sets) >= self.split_call_min_sets
-                and not any(isinstance(s, CommitteeSet) for s in sets)
+                and not any(isinstance(s, (CommitteeSet, SpanSet)) for s in sets)
                 and sum(self._slot_ctxs) > 0 and all(self._slot_ctxs)):
             return self._split_call(sets)
         return self._queue_call(sets, batchable)
@@ -664,8 +706,8 @@ class GpuBlsVerifier:
 
     def _call(self, ctx, reqs, worker_id: int = 0):
         """One GPU submission per pubkey form: table-index requests as one message
-        (bls_gpu_verify), requests holding a committee set as a message of their own
-        (bls_gpu_verify_committees), raw-key requests as the reference's worker messages (jobs
+        (bls_gpu_verify), requests holding a committee or span set as a message of their own
+        (bls_gpu_verify_committees; bls_gpu_verify_spans once any of them is a span), raw-key requests as the reference's worker messages (jobs
         until >= 128 sets each) through one bls_gpu_verify_many."""
         def is_raw(req):
             if any(isinstance(s, dict) for s in req[1]):
@@ -682,7 +724,10 @@ class GpuBlsVerifier:
             if raw == "committee":
                 pb = pack_requests([reqs[k] for k in idx])
                 t1 = time.perf_counter()
-                v, stats = ctx.verify_committees_packed(pb)
+                if pb.set_span_off is not None:
+                    v, stats = ctx.verify_spans_packed(pb)
+                else:
+                    v, stats = ctx.verify_committees_packed(pb)
             elif raw:
                 msgs, cur, n = [], [], 0
                 for k in idx:
