@@ -528,6 +528,38 @@ int bls_gpu_fp_mul_test(bls_gpu_ctx* ctx, const uint8_t* a48, const uint8_t* b48
 int bls_gpu_field_op_test(bls_gpu_ctx* ctx, uint32_t op, const uint32_t* in, uint32_t n, uint32_t* out);
 int bls_gpu_field_op_shape(uint32_t op, uint32_t* in_words, uint32_t* out_words);
 
+/* Device curve-op self-test: one lane per record runs ONE curve-level function of the verify
+ * path, the production function itself in the translation-unit flavour production compiles
+ * it in, one launch per call.  Fp values travel as 12 little-endian 32-bit words in
+ * Montgomery form, exactly what production passes between these kernels; nothing on the
+ * device converts or canonicalises them.  `in` holds n records of in_words words, `out`
+ * receives n records of out_words (bls_gpu_curve_op_shape).  op: a base id
+ * (lodestar_amd/csrc/kernels/curve_op_ids.hpp COP_*, tests/_curvevec.py), ORed with
+ * BLS_CURVE_OP_D28 for the 28-bit-digit flavours.  -2: unknown op, or an op in a flavour it
+ * does not exist in.
+ *   0 FROM_BE64       fp_from_be64_words (cols, d28)       16 big-endian words -> Fp
+ *   1 H2F             hash_to_field_fp2_x2 (cols, d28)     8 message words -> u0, u1
+ *   2 SSWU            map_to_curve_sswu (cols)             u -> x, y
+ *   3 SSWU_FAST       map_to_curve_sswu_fast (d28: k_pre)  u -> ok word, x, y
+ *   4 ISO_AFF         iso_map_g2 (cols)                    x, y -> inf word, x, y
+ *   5 ISO_JAC         k_chain.hip iso_jac_nl (d28 + Fp2 primitive)   x, y -> X, Y, Z
+ *   6 CLEAR_COFACTOR  g2_clear_cofactor + jac_to_aff (cols)          inf, x, y -> inf, x, y
+ *   7 CHAIN_H         k_chain.hip chain_role_h (d28 + Fp2 primitive) q0, q1 (8 Fp) ->
+ *                     chain_st byte (1: H = O, HQ left zero), HQ (4 Fp)
+ * Two more ops add no kernel and no arithmetic: they fill a zeroed set of pipeline buffers
+ * with the records alone and call the production launchers (both BLS_CURVE_OP_D28 only).
+ *   8 MILLER  the split SIMT Miller loops (k_mlq, then k_mlf or k_mlf2): record = RP (Jacobian
+ *             G1: x, y, z, any z), HQ (affine G2), the item's product domain, per_lane (1, 2,
+ *             4 or 3 = two lanes per item; record 0's counts) -> f (12 Fp, Fp12 memory order).
+ *             Items [0, n) run as one first-pass launch: per_lane consecutive items of one
+ *             domain share one f (the first holds the product, the others exactly 1).
+ *             At most 1,024 items.
+ *   9 FE      F (12 Fp) -> two words: FE(F) == 1 by the SIMT chunk kernel and by the
+ *             cooperative one, each F its own one-request, one-set chunk */
+#define BLS_CURVE_OP_D28 0x100u
+int bls_gpu_curve_op_test(bls_gpu_ctx* ctx, uint32_t op, const uint32_t* in, uint32_t n, uint32_t* out);
+int bls_gpu_curve_op_shape(uint32_t op, uint32_t* in_words, uint32_t* out_words);
+
 /* Interpreter test: the cooperative program `name` of the loaded table run once on each
  * of n_frames frames of n_slots raw Fp values (12 little-endian words each, Montgomery
  * form, any representative below 3p); frames_out receives the raw frames after the run

@@ -72,6 +72,8 @@ SYMBOLS = (
     "bls_gpu_fp_mul_test",
     "bls_gpu_field_op_test",
     "bls_gpu_field_op_shape",
+    "bls_gpu_curve_op_test",
+    "bls_gpu_curve_op_shape",
     "bls_gpu_coop_run_test",
     "bls_gpu_fpm_bench",
     "bls_gpu_coop_probe",
@@ -108,6 +110,7 @@ SSZ_DEPOSIT_MESSAGE = 0x600 | 88
 SSZ_FORK_DATA = 0x700 | 36
 SSZ_SIGNING_DATA = 0x800 | 64
 FIELD_OP_D28 = 0x100  # BLS_FIELD_OP_D28: the field-op self-test's 28-bit-digit kernels
+CURVE_OP_D28 = 0x100  # BLS_CURVE_OP_D28: the curve-op self-test's 28-bit-digit flavours
 DEBUG_FORCE_EXACT = 1
 DEBUG_NO_MSG_DEDUP = 2
 DEBUG_NO_MERGED_CHECK = 4
@@ -324,6 +327,10 @@ def bind(lib: ctypes.CDLL) -> ctypes.CDLL:
         lib.bls_gpu_field_op_test.restype = i32
         lib.bls_gpu_field_op_shape.argtypes = [u32, u32p, u32p]
         lib.bls_gpu_field_op_shape.restype = i32
+        lib.bls_gpu_curve_op_test.argtypes = [vp, u32, vp, u32, vp]
+        lib.bls_gpu_curve_op_test.restype = i32
+        lib.bls_gpu_curve_op_shape.argtypes = [u32, u32p, u32p]
+        lib.bls_gpu_curve_op_shape.restype = i32
         lib.bls_gpu_coop_run_test.argtypes = [vp, ctypes.c_char_p, vp, u32, u32, vp, vp]
         lib.bls_gpu_coop_run_test.restype = i32
         dp = ctypes.POINTER(ctypes.c_double)

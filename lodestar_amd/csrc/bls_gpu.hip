@@ -59,6 +59,7 @@
 #include "bls/pk_table.hpp"
 #include "bls/plan.hpp"
 #include "launchers.hpp"
+#include "kernels/curve_op_ids.hpp"
 
 using namespace bls;
 
@@ -2522,6 +2523,134 @@ extern "C" int bls_gpu_field_op_test(bls_gpu_ctx* ctx, uint32_t op, const uint32
   HIPC(ctx, hipMemcpyAsync(din, in, in_sz, hipMemcpyHostToDevice, s));
   HIPC(ctx, hipMemsetAsync(dout, 0, out_sz, s));
   HIPC(ctx, launch_k_field_op(op, din, n, dout, s));
+  HIPC(ctx, hipMemcpyAsync(out, dout, out_sz, hipMemcpyDeviceToHost, s));
+  HIPC(ctx, hipStreamSynchronize(s));
+  return 0;
+}
+
+extern "C" int bls_gpu_curve_op_shape(uint32_t op, uint32_t* in_words, uint32_t* out_words) {
+  return curve_op_shape(op, in_words, out_words);
+}
+
+// COP_MILLER: the split SIMT Miller loops through launch_k_mlqf on a zero-initialised
+// PipeBufs that holds only what the launched kernels read.  Record: RP (x, y, z: Jacobian
+// G1, any z), HQ (x.c0, x.c1, y.c0, y.c1), the item's product domain, per_lane (record 0's
+// counts: 1, 2, 4 or MLF_PAIR); out: f[i].  PipeBufs fields dereferenced (kernels/k_mlq.hip):
+//   ml_live    chain_live[i]; set_unit only when non-null (left null); n_sets by value
+//   mlq_lane   chain (CH_RP, CH_HQ), the line buffer
+//   mlf_lane   ml_dom[i] (when non-null), indiv_vbase by value, f[i], the line buffer
+//   k_mlf2     f[i], the line buffer
+// and launch_k_mlqf reads mlf_pl on the host.  msg_rep, set_unit and everything else stay null.
+static int curve_miller_test(bls_gpu_ctx* ctx, const uint32_t* in, uint32_t n, uint32_t* out) {
+  const uint32_t iw = (uint32_t)curve_op_in_words(COP_MILLER), per_lane = in[iw - 1];
+  if (n > COP_MILLER_MAX || !(per_lane == 1 || per_lane == 2 || per_lane == 4 || per_lane == MLF_PAIR)) {
+    snprintf(ctx->err, sizeof(ctx->err), "curve op MILLER: %u items, per_lane %u", n, per_lane);
+    return -2;
+  }
+  std::vector<uint32_t> chain((size_t)CHAIN_WORDS * 12 * n, 0u), live(n, 1u), dom(n);
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint32_t* r = in + (size_t)iw * i;
+    uint32_t* row = chain.data() + (size_t)CHAIN_WORDS * 12 * i;
+    memcpy(row + 12 * CH_RP, r, 4 * 36);
+    memcpy(row + 12 * CH_HQ, r + 36, 4 * 48);
+    dom[i] = r[84];
+  }
+  auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  const size_t chain_sz = al(4 * chain.size()), w_sz = al(4ull * n), f_sz = al(sizeof(Fp12) * (size_t)n),
+               line_sz = al(4 * mlq_line_words(n));
+  if (ensure_dev(ctx, chain_sz + 2 * w_sz + f_sz + line_sz)) return -1;
+  uint8_t* p = ctx->dev_ws;
+  PipeBufs b;
+  memset(&b, 0, sizeof(b));
+  b.n_sets = n;
+  b.indiv_vbase = n;
+  b.mlf_pl = per_lane;
+  b.chain = (Fp*)p;
+  b.chain_live = (uint32_t*)(p + chain_sz);
+  uint32_t* d_dom = (uint32_t*)(p + chain_sz + w_sz);
+  b.ml_dom = d_dom;
+  b.f = (Fp12*)(p + chain_sz + 2 * w_sz);
+  uint32_t* lines = (uint32_t*)(p + chain_sz + 2 * w_sz + f_sz);
+  hipStream_t s = ctx->stream;
+  HIPC(ctx, hipMemcpyAsync(b.chain, chain.data(), 4 * chain.size(), hipMemcpyHostToDevice, s));
+  HIPC(ctx, hipMemcpyAsync(b.chain_live, live.data(), 4ull * n, hipMemcpyHostToDevice, s));
+  HIPC(ctx, hipMemcpyAsync(d_dom, dom.data(), 4ull * n, hipMemcpyHostToDevice, s));
+  HIPC(ctx, hipMemsetAsync(b.f, 0, f_sz, s));
+  HIPC(ctx, launch_k_mlqf(b, 0, n, false, lines, s));
+  HIPC(ctx, hipMemcpyAsync(out, b.f, sizeof(Fp12) * (size_t)n, hipMemcpyDeviceToHost, s));
+  HIPC(ctx, hipStreamSynchronize(s));
+  return 0;
+}
+
+// COP_FE: FE(F) == 1 for n Fp12 values, each its own one-request, one-set chunk, through the
+// SIMT chunk kernel and through the cooperative one over the same buffers; out: chunk_ok of
+// each form.  PipeBufs fields dereferenced (k_chunk_simt, k_chunk_coop):
+//   n_chunks by value; chunk_off[c], chunk_off[c + 1]; chunk_reqs[k]; req_status[r];
+//   req_off[r], req_off[r + 1]; f[i]; chunk_ok[c]; set_unit, unit_off, chunk_fe only when
+//   non-null (left null); sigagg = 0, so n_sets and unit_base are not used
+// plus the SIMT form's four Fp12 of save per task and the context's program table.
+static int curve_fe_test(bls_gpu_ctx* ctx, const uint32_t* in, uint32_t n, uint32_t* out) {
+  std::vector<uint32_t> idx(n + 1);
+  for (uint32_t i = 0; i <= n; ++i) idx[i] = i;
+  auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  const size_t f_sz = al(sizeof(Fp12) * (size_t)n), w_sz = al(4ull * (n + 1));
+  if (ensure_dev(ctx, 5 * f_sz + 4 * w_sz)) return -1;
+  uint8_t* p = ctx->dev_ws;
+  PipeBufs b;
+  memset(&b, 0, sizeof(b));
+  b.n_chunks = n;
+  b.n_reqs = n;
+  b.n_sets = n;
+  b.f = (Fp12*)p;
+  Fp12* save = (Fp12*)(p + f_sz);
+  uint32_t* d_idx = (uint32_t*)(p + 5 * f_sz);
+  b.chunk_off = b.chunk_reqs = b.req_off = d_idx;  // chunk c = request c = set c
+  b.req_status = (int32_t*)(p + 5 * f_sz + w_sz);
+  int32_t* ok_simt = (int32_t*)(p + 5 * f_sz + 2 * w_sz);
+  int32_t* ok_coop = (int32_t*)(p + 5 * f_sz + 3 * w_sz);
+  hipStream_t s = ctx->stream;
+  HIPC(ctx, hipMemcpyAsync(b.f, in, sizeof(Fp12) * (size_t)n, hipMemcpyHostToDevice, s));
+  HIPC(ctx, hipMemcpyAsync(d_idx, idx.data(), 4ull * (n + 1), hipMemcpyHostToDevice, s));
+  HIPC(ctx, hipMemsetAsync(b.req_status, 0, w_sz, s));
+  HIPC(ctx, hipMemsetAsync(ok_simt, 0xFF, 2 * w_sz, s));  // -1: a kernel that writes nothing shows
+  b.chunk_ok = ok_simt;
+  HIPC(ctx, launch_k_chunk_simt(b, save, s));
+  b.chunk_ok = ok_coop;
+  HIPC(ctx, launch_k_chunk_coop(b, ctx->coop, s));
+  std::vector<int32_t> ok(2 * (size_t)n);
+  HIPC(ctx, hipMemcpyAsync(ok.data(), ok_simt, 4ull * n, hipMemcpyDeviceToHost, s));
+  HIPC(ctx, hipMemcpyAsync(ok.data() + n, ok_coop, 4ull * n, hipMemcpyDeviceToHost, s));
+  HIPC(ctx, hipStreamSynchronize(s));
+  for (uint32_t i = 0; i < n; ++i) {
+    out[2 * i] = (uint32_t)ok[i];
+    out[2 * i + 1] = (uint32_t)ok[n + i];
+  }
+  return 0;
+}
+
+// One curve-level function per lane on Montgomery-form words (kernels/curve_ops.hpp): n
+// records of the op's in_words in, n of its out_words out; chain_role_h's rows and bytes
+// live in zeroed workspace behind them.
+extern "C" int bls_gpu_curve_op_test(bls_gpu_ctx* ctx, uint32_t op, const uint32_t* in, uint32_t n, uint32_t* out) {
+  CTX_LOCK(ctx);
+  HIPC(ctx, hipSetDevice(ctx->device));
+  uint32_t iw = 0, ow = 0;
+  if (curve_op_shape(op, &iw, &ow) != 0) {
+    snprintf(ctx->err, sizeof(ctx->err), "unknown curve op 0x%x", op);
+    return -2;
+  }
+  if (n == 0) return 0;
+  if ((op & ~COP_D28_FLAG) == COP_MILLER) return curve_miller_test(ctx, in, n, out);
+  if ((op & ~COP_D28_FLAG) == COP_FE) return curve_fe_test(ctx, in, n, out);
+  const size_t in_sz = 4ull * iw * n, out_sz = 4ull * ow * n, in_al = (in_sz + 255) & ~(size_t)255,
+               out_al = (out_sz + 255) & ~(size_t)255, ws_sz = curve_op_ws_bytes(op, n);
+  if (ensure_dev(ctx, in_al + out_al + ws_sz)) return -1;
+  uint32_t *din = (uint32_t*)ctx->dev_ws, *dout = (uint32_t*)(ctx->dev_ws + in_al);
+  void* dws = ws_sz ? ctx->dev_ws + in_al + out_al : nullptr;
+  hipStream_t s = ctx->stream;
+  HIPC(ctx, hipMemcpyAsync(din, in, in_sz, hipMemcpyHostToDevice, s));
+  HIPC(ctx, hipMemsetAsync(dout, 0, out_al + ws_sz, s));
+  HIPC(ctx, launch_k_curve_op(op, din, n, dout, dws, s));
   HIPC(ctx, hipMemcpyAsync(out, dout, out_sz, hipMemcpyDeviceToHost, s));
   HIPC(ctx, hipStreamSynchronize(s));
   return 0;

@@ -35,6 +35,7 @@
 #define BLS_FP_D28 1
 #define BLS_FP2_PRIM 1
 #include "../launchers.hpp"
+#include "curve_op_ids.hpp"
 
 using namespace bls;
 
@@ -293,5 +294,39 @@ hipError_t launch_k_chain(const PipeBufs& b, hipStream_t s, uint32_t roles) {
   if (roles == 0) return hipSuccess;
   k_chain<<<(uint32_t)__builtin_popcount(roles) * nb, BLS_BLOCK, 0, s>>>(b, nb, roles);
   if (roles != 0x4u) k_chain_done<<<nb, BLS_BLOCK, 0, s>>>(b);
+  return hipGetLastError();
+}
+
+// Curve-op self-test (kernels/curve_ops.hpp), the two ops whose functions are local to this
+// file: one lane per record calls iso_jac_nl / chain_role_h as k_chain does, on Fp values
+// in the words production hands them (q: 8 Fp per record, b.q's layout).  chain_role_h
+// writes record i's row of `chain` and byte 4 i of `st` (both zeroed by the caller); the
+// lane then copies its own byte and HQ out.  k_chain's launch bounds and occupancy, so the
+// callees' frames are reserved as for k_chain.
+__global__ __launch_bounds__(BLS_BLOCK) BLS_CHAIN_ATTR void k_curve_op_chain(uint32_t op, const Fp* in, uint32_t n,
+                                                                            uint32_t* out, Fp* chain, uint8_t* st) {
+  const uint32_t i = blockIdx.x * BLS_BLOCK + threadIdx.x;
+  if (i >= n) return;
+  if (op == COP_ISO_JAC) {
+    // straight into the record: a local point would sit in the kernel's frame under the callee's
+    iso_jac_nl(reinterpret_cast<G2J*>(out + (size_t)curve_op_out_words(COP_ISO_JAC) * i), in + 4ull * i);
+    return;
+  }
+  chain_role_h(chain, in, st, i);
+  uint32_t* o = out + (size_t)curve_op_out_words(COP_CHAIN_H) * i;
+  o[0] = st[4 * i];
+  Fp* hq = reinterpret_cast<Fp*>(o + 1);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) hq[k] = chain[(size_t)CHAIN_WORDS * i + CH_HQ + k];
+}
+
+static_assert(sizeof(G2J) == 4 * curve_op_out_words(COP_ISO_JAC) && sizeof(Fp) == 48, "record layouts");
+
+hipError_t launch_k_curve_op_chain(uint32_t op, const uint32_t* in, uint32_t n, uint32_t* out, void* ws,
+                                   hipStream_t s) {
+  if (!curve_op_in_chain_tu(op) || (op == COP_CHAIN_H && !ws)) return hipErrorInvalidValue;
+  Fp* chain = static_cast<Fp*>(ws);
+  uint8_t* st = reinterpret_cast<uint8_t*>(chain + (size_t)CHAIN_WORDS * n);
+  k_curve_op_chain<<<bls_grid_for(n), BLS_BLOCK, 0, s>>>(op, reinterpret_cast<const Fp*>(in), n, out, chain, st);
   return hipGetLastError();
 }

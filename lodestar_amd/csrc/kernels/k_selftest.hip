@@ -3,6 +3,7 @@
 // one wave runs alone, throughput when every CU is busy).
 #include "../launchers.hpp"
 #include "field_ops.hpp"
+#include "curve_ops.hpp"
 
 using namespace bls;
 
@@ -45,4 +46,25 @@ hipError_t launch_k_field_op(uint32_t op, const uint32_t* in, uint32_t n, uint32
   if (field_op_shape(op, nullptr, nullptr) != 0) return hipErrorInvalidValue;
   if (op & FOP_D28_FLAG) return launch_k_field_op_d28(op & ~FOP_D28_FLAG, in, n, out, s);
   return field_op_launch(op, in, n, out, s);
+}
+
+// the curve-op self-test (kernels/curve_ops.hpp): the 32-bit column flavour here, the
+// 28-bit-digit one in kernels/k_selftest_d28.hip, iso_jac_nl and chain_role_h beside
+// k_chain in kernels/k_chain.hip
+int curve_op_shape(uint32_t op, uint32_t* in_words, uint32_t* out_words) {
+  const uint32_t base = op & ~COP_D28_FLAG;
+  if (base >= COP_COUNT || !(curve_op_flavours(base) & ((op & COP_D28_FLAG) ? 2u : 1u))) return -2;
+  if (in_words) *in_words = (uint32_t)curve_op_in_words(base);
+  if (out_words) *out_words = (uint32_t)curve_op_out_words(base);
+  return 0;
+}
+size_t curve_op_ws_bytes(uint32_t op, uint32_t n) {
+  return (op & ~COP_D28_FLAG) == COP_CHAIN_H ? (sizeof(Fp) * CHAIN_WORDS + 4u) * (size_t)n : 0;
+}
+hipError_t launch_k_curve_op(uint32_t op, const uint32_t* in, uint32_t n, uint32_t* out, void* ws, hipStream_t s) {
+  const uint32_t base = op & ~COP_D28_FLAG;
+  if (curve_op_shape(op, nullptr, nullptr) != 0 || curve_op_on_host(base)) return hipErrorInvalidValue;
+  if (curve_op_in_chain_tu(base)) return launch_k_curve_op_chain(base, in, n, out, ws, s);
+  if (op & COP_D28_FLAG) return launch_k_curve_op_d28(base, in, n, out, s);
+  return curve_op_launch(base, in, n, out, s);
 }

@@ -4,9 +4,14 @@
 #define BLS_FP_D28 1
 #include "../launchers.hpp"
 #include "field_ops.hpp"
+#include "curve_ops.hpp"
 
 using namespace bls;
 
 hipError_t launch_k_field_op_d28(uint32_t op, const uint32_t* in, uint32_t n, uint32_t* out, hipStream_t s) {
   return field_op_launch(op, in, n, out, s);
+}
+
+hipError_t launch_k_curve_op_d28(uint32_t op, const uint32_t* in, uint32_t n, uint32_t* out, hipStream_t s) {
+  return curve_op_launch(op, in, n, out, s);
 }

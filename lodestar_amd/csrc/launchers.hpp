@@ -90,6 +90,15 @@ hipError_t launch_k_fp_mul_test(const uint8_t* a, const uint8_t* b, uint32_t n, 
 int field_op_shape(uint32_t op, uint32_t* in_words, uint32_t* out_words);
 hipError_t launch_k_field_op(uint32_t op, const uint32_t* in, uint32_t n, uint32_t* out, hipStream_t s);
 hipError_t launch_k_field_op_d28(uint32_t op, const uint32_t* in, uint32_t n, uint32_t* out, hipStream_t s);
+// curve-op self-test (kernels/curve_ops.hpp): op = base id | COP_D28_FLAG; curve_op_shape:
+// record sizes in words, -2 for an unknown op or a flavour the op does not exist in;
+// ws: curve_op_ws_bytes(op, n) of zeroed device memory (COP_CHAIN_H's chain rows and bytes)
+int curve_op_shape(uint32_t op, uint32_t* in_words, uint32_t* out_words);
+size_t curve_op_ws_bytes(uint32_t op, uint32_t n);
+hipError_t launch_k_curve_op(uint32_t op, const uint32_t* in, uint32_t n, uint32_t* out, void* ws, hipStream_t s);
+hipError_t launch_k_curve_op_d28(uint32_t op, const uint32_t* in, uint32_t n, uint32_t* out, hipStream_t s);
+hipError_t launch_k_curve_op_chain(uint32_t op, const uint32_t* in, uint32_t n, uint32_t* out, void* ws,
+                                   hipStream_t s);
 hipError_t launch_k_fpm_chain(bls::Fp* io, uint32_t lanes, uint32_t iters, hipStream_t s);
 size_t kernel_probe_out_bytes(const char* name);
 hipError_t launch_kernel_probe(const char* name, void* out, uint32_t lanes, hipStream_t s);

@@ -318,6 +318,20 @@ int hs_iso_map_jac(const uint8_t* xy192, uint8_t* out192) {
   wr_fp2(a.y, out192 + 96);
   return 1;
 }
+// the affine isogeny (iso_map_g2: k_h2c, k_sign, the exact path), same layout; 0 for infinity
+int hs_iso_map_g2(const uint8_t* xy192, uint8_t* out192) {
+  G2A p;
+  p.inf = false;
+  p.x = rd_fp2(xy192);
+  p.y = rd_fp2(xy192 + 96);
+  const G2A a = iso_map_g2(p);
+  if (a.inf) return 0;
+  wr_fp2(a.x, out192);
+  wr_fp2(a.y, out192 + 96);
+  return 1;
+}
+// 512 bits -> Fp (fp_from_be64_words): 16 big-endian words, most significant first
+void hs_fp_from_be64_words(const uint32_t* w16, uint8_t* out48) { wr_fp(fp_from_be64_words(w16), out48); }
 void hs_g2_clear_cofactor(const uint8_t* g2, uint8_t* out192) {
   g2_serialize192(jac_to_aff(g2_clear_cofactor(jac_from_aff(rd_g2(g2)))), out192);
 }
