@@ -560,6 +560,29 @@ int bls_gpu_field_op_shape(uint32_t op, uint32_t* in_words, uint32_t* out_words)
 int bls_gpu_curve_op_test(bls_gpu_ctx* ctx, uint32_t op, const uint32_t* in, uint32_t n, uint32_t* out);
 int bls_gpu_curve_op_shape(uint32_t op, uint32_t* in_words, uint32_t* out_words);
 
+/* Device tower-op self-test: one lane per record runs ONE function of the Fp6 / Fp12 tower
+ * the SIMT verify path runs in every Miller-loop step and final exponentiation, the
+ * production function itself in a translation-unit flavour production compiles it in.  Fp
+ * values travel as 12 little-endian 32-bit words in Montgomery form (raw value in [0, p));
+ * an Fp6 is 6 Fp, an Fp12 12 Fp in memory order (c0.c0, c0.c1, c0.c2, c1.c0, c1.c1, c1.c2),
+ * a line l0, l2, l3.  Nothing on the device converts or canonicalises around the call.  op: a
+ * base id (lodestar_amd/csrc/kernels/tower_op_ids.hpp TOP_*, tests/_towervec.py), ORed
+ * with BLS_TOWER_OP_D28 for the 28-bit-digit flavours.  -2: unknown op, or an op in a
+ * flavour it does not exist in (nothing runs, `out` is not written).
+ *   0 FP6_MUL (cols, d28)   1 FP6_MUL_01 (cols)   2 FP6_MUL_1 (cols)   3 FP6_INV (d28)
+ *   4 FP12_MUL (cols)   5 FP12_SQR (cols)   6 FP12_MUL_LINE (cols)
+ *   7 FP12_INV (d28)    8 FP12_FROB (d28)   9 FP12_FROB2 (d28)
+ *   10 FIN_MUL12M, 11 FIN_MUL12M_CONJ, 12 FIN_CYC_SQR, 13 FIN_EXP_X_M: k_fin_simt.hip's
+ *      file-local functions (d28), operands in device memory as there
+ *   14 MLQ_SQR12, 15 MLQ_MUL_LINE12, 16 MLQ_MUL_LINE2 (f, line, line): k_mlq.hip (d28 + Fp2
+ *      primitive); 17 MLQ_SQR12_PAIR, 18 MLQ_MUL_LINE12_PAIR: the two-lane halves, output
+ *      lane 2k's Fp12 then lane 2k + 1's
+ *   19 MLQ_LINES (d28): RP (Jacobian G1 x, y, z, z != 0), HQ (4 Fp) -> the 68 lines k_mlq
+ *      writes for the item (event-major, l0, l2, l3 each); at most 64 items */
+#define BLS_TOWER_OP_D28 0x100u
+int bls_gpu_tower_op_test(bls_gpu_ctx* ctx, uint32_t op, const uint32_t* in, uint32_t n, uint32_t* out);
+int bls_gpu_tower_op_shape(uint32_t op, uint32_t* in_words, uint32_t* out_words);
+
 /* Interpreter test: the cooperative program `name` of the loaded table run once on each
  * of n_frames frames of n_slots raw Fp values (12 little-endian words each, Montgomery
  * form, any representative below 3p); frames_out receives the raw frames after the run

@@ -74,6 +74,8 @@ SYMBOLS = (
     "bls_gpu_field_op_shape",
     "bls_gpu_curve_op_test",
     "bls_gpu_curve_op_shape",
+    "bls_gpu_tower_op_test",
+    "bls_gpu_tower_op_shape",
     "bls_gpu_coop_run_test",
     "bls_gpu_fpm_bench",
     "bls_gpu_coop_probe",
@@ -331,6 +333,10 @@ def bind(lib: ctypes.CDLL) -> ctypes.CDLL:
         lib.bls_gpu_curve_op_test.restype = i32
         lib.bls_gpu_curve_op_shape.argtypes = [u32, u32p, u32p]
         lib.bls_gpu_curve_op_shape.restype = i32
+        lib.bls_gpu_tower_op_test.argtypes = [vp, u32, vp, u32, vp]
+        lib.bls_gpu_tower_op_test.restype = i32
+        lib.bls_gpu_tower_op_shape.argtypes = [u32, u32p, u32p]
+        lib.bls_gpu_tower_op_shape.restype = i32
         lib.bls_gpu_coop_run_test.argtypes = [vp, ctypes.c_char_p, vp, u32, u32, vp, vp]
         lib.bls_gpu_coop_run_test.restype = i32
         dp = ctypes.POINTER(ctypes.c_double)

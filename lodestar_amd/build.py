@@ -110,7 +110,7 @@ def _check_scratch(src: Path, kernels: list[dict]) -> None:
 # the MAD-peak, self-test and latency probes): never launched by a verify call, so they do
 # not set the per-queue figure a verifier context is admitted against
 FIXTURE_TUS = ("k_sign", "k_probe", "k_peak", "k_selftest", "k_selftest_d28")
-FIXTURE_KERNELS = ("k_coop_probe", "k_coop_run_test", "k_curve_op_chain")
+FIXTURE_KERNELS = ("k_coop_probe", "k_coop_run_test", "k_curve_op_chain", "k_tower_op_fin", "k_tower_op_mlq")
 
 
 def _plain_name(mangled: str) -> str:

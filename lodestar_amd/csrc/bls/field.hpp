@@ -1307,8 +1307,10 @@ BLS_HD Fp2 fp2_conj(const Fp2& a) { return Fp2{a.c0, fp_neg(a.c1)}; }
 BLS_HD Fp2 fp2_half(const Fp2& a) { return Fp2{fp_half(a.c0), fp_half(a.c1)}; }
 BLS_HD Fp2 fp2_mul_fp(const Fp2& a, const Fp& b) { return Fp2{fp_mul(a.c0, b), fp_mul(a.c1, b)}; }
 
-// Karatsuba with unreduced pre-additions (operands < 2p; reduced ones measured 3 % slower
-// at the plateau, profiles/r03_ab_fp2_preadd.json)
+// Karatsuba with unreduced pre-additions (reduced ones measured 3 % slower at the plateau,
+// profiles/r03_ab_fp2_preadd.json).  The tower passes canonical operands here (every caller
+// below hands over outputs of fp_add / fp_sub / fp_mul), so the two inner sums are <= 2p - 2;
+// the unreduced Karatsuba sums of Fp6 and of the line products go to fp2_mul_s instead.
 BLS_HD Fp2 fp2_mul(const Fp2& a, const Fp2& b) {
 #if defined(__HIP_DEVICE_COMPILE__) && defined(BLS_FP2_PRIM)
   return fp2_mul_prim(a, b);
@@ -1324,7 +1326,8 @@ BLS_HD Fp2 fp2_mul(const Fp2& a, const Fp2& b) {
 // fp2_add_nr of canonical values): a0 b0 and a1 b1 < 4p^2, and (a0 + a1) brought back
 // under 2p times (b0 + b1) < 4p is < 8p^2 < 2^384 p, inside the Montgomery product's
 // input bound (its output < 2p, then canonical); output canonical.  Saves the four
-// reductions of the pre-additions for one here (tests: test_hostsim.py::test_fp2_mul_s)
+// reductions of the pre-additions for one here (tests: test_hostsim.py::test_fp2_mul_s; on
+// the device through every tower call site at its largest operand: tests/test_gpu_tower_ops.py)
 BLS_HD Fp2 fp2_mul_s(const Fp2& a, const Fp2& b) {
 #if defined(__HIP_DEVICE_COMPILE__) && defined(BLS_FP2_PRIM)
   return fp2_mul_prim(a, b);
@@ -1428,7 +1431,12 @@ BLS_HD Fp6 fp6_mul(const Fp6& a, const Fp6& b) {
   Fp2 t0 = fp2_mul(a.c0, b.c0);
   Fp2 t1 = fp2_mul(a.c1, b.c1);
   Fp2 t2 = fp2_mul(a.c2, b.c2);
-  // (the Karatsuba pre-additions stay unreduced: fp2_mul_s)
+  // (the Karatsuba pre-additions stay unreduced: fp2_mul_s).  a and b are canonical at every
+  // caller (fp12_mul, fp12_sqr, fp12_inv, kernels/k_mlq.hip sqr12, kernels/k_fin_simt.hip mul12m
+  // pass inputs or fp6_add / fp6_neg / fp6_mul_v results), so each of the six sums below has
+  // coefficients <= 2p - 2 in all three flavours: inside fp2_mul_s's (a0 + a1) < 4p and inside
+  // the rows' < 2p (BLS_FP2_PRIM).  Raw p - 1 operands reach 2p - 2 at all three sites; through
+  // fp12_mul's third product the raw (p - 1) / 2 operands do (test_towervec_cpu.py).
   Fp2 c0 = fp2_sub(fp2_sub(fp2_mul_s(fp2_add_nr(a.c1, a.c2), fp2_add_nr(b.c1, b.c2)), t1), t2);
   c0 = fp2_add(fp2_mul_xi(c0), t0);
   Fp2 c1 = fp2_sub(fp2_sub(fp2_mul_s(fp2_add_nr(a.c0, a.c1), fp2_add_nr(b.c0, b.c1)), t0), t1);
@@ -1445,6 +1453,9 @@ BLS_HD Fp6 fp6_mul_01(const Fp6& a, const Fp2& d0, const Fp2& d1) {
   Fp2 a0d0 = fp2_mul(a.c0, d0);
   Fp2 a1d1 = fp2_mul(a.c1, d1);
   Fp2 c0 = fp2_add(a0d0, fp2_mul_xi(fp2_mul(a.c2, d1)));
+  // a, d0, d1 canonical at every caller (d1 is l2 or the REDUCED fp2_add(l2, l3); fp12_mul_line2
+  // passes fp2_sub results): both sums <= 2p - 2.  An unreduced l2 + l3 would make d0 + d1 3p - 3,
+  // past the rows' < 2p.
   Fp2 c1 = fp2_sub(fp2_sub(fp2_mul_s(fp2_add_nr(a.c0, a.c1), fp2_add_nr(d0, d1)), a0d0), a1d1);
   Fp2 c2 = fp2_add(a1d1, fp2_mul(a.c2, d0));
   return Fp6{c0, c1, c2};
@@ -1491,8 +1502,10 @@ BLS_NOINLINE Fp12 fp12_sqr(const Fp12& a) {
 
 // f * (l0 + l2 w^2 + l3 w^3): the M-twist line shape (arkworks mul_by_014)
 BLS_NOINLINE Fp12 fp12_mul_line(const Fp12& f, const Fp2& l0, const Fp2& l2, const Fp2& l3) {
-  Fp6 aa = fp6_mul_01(f.c0, l0, l2);
+  Fp6 aa = fp6_mul_01(f.c0, l0, l2);  // sums <= 2p - 2, reached by raw p - 1 operands
   Fp6 bb = fp6_mul_1(f.c1, l3);
+  // reduced sums in: <= 2p - 2 again, reached when f.c0 + f.c1 and l2 + l3 are p - 1 (raw
+  // (p - 1) / 2 operands; all-p-1 inputs give p - 2 here)
   Fp6 c1 = fp6_sub(fp6_sub(fp6_mul_01(fp6_add(f.c0, f.c1), l0, fp2_add(l2, l3)), aa), bb);
   Fp6 c0 = fp6_add(aa, fp6_mul_v(bb));
   return Fp12{c0, c1};
@@ -1502,7 +1515,10 @@ BLS_NOINLINE Fp12 fp12_mul_line(const Fp12& f, const Fp2& l0, const Fp2& l2, con
 // the lines first (6 Fp2 products, w^6 = xi, no w^1 term: P.c0 = (A0, A2, A4), P.c1 =
 // (0, A3, A5)), then f * P by Karatsuba over Fp6 (6 + 5 + 6): 23 Fp2 products instead of
 // the 26 of two fp12_mul_line calls.  Same value as fp12_mul_line(fp12_mul_line(f, L), M)
-// (test_hostsim.py::test_fp12_mul_line2); the shared-f Miller loops (kernels/k_mlq.hip).
+// (test_hostsim.py::test_fp12_mul_line2; on the device: tests/test_gpu_tower_ops.py
+// fp12_mul_line2-mlq); the shared-f Miller loops (kernels/k_mlq.hip).  The lines are canonical
+// (load_line of store_line's products), so the six line sums below are <= 2p - 2, reached by raw
+// p - 1 lines; p0, a3, a5 and the sums into the last fp6_mul are fp2_add / fp2_sub results.
 BLS_HD Fp12 fp12_mul_line2(const Fp12& f, const Fp2& l0, const Fp2& l2, const Fp2& l3, const Fp2& m0,
                            const Fp2& m2, const Fp2& m3) {
   const Fp2 m00 = fp2_mul(l0, m0), m22 = fp2_mul(l2, m2), m33 = fp2_mul(l3, m3);
@@ -1520,7 +1536,8 @@ BLS_HD Fp12 fp12_mul_line2(const Fp12& f, const Fp2& l0, const Fp2& l2, const Fp
 // One f over two lanes (kernels/k_mlq.hip k_mlf2): each half computes one part of the
 // products (_prod), the halves swap their parts, and both finish alike (_join).  Host-
 // tested against fp12_sqr / fp12_mul_line with both halves run one after the other
-// (test_hostsim.py::test_fp12_pair_halves).
+// (test_hostsim.py::test_fp12_pair_halves; on the device with k_mlf2's own lane exchange:
+// tests/test_gpu_tower_ops.py sqr12_pair-mlq, mul_line12_pair-mlq).
 //   (A + B w)^2 = (s - ab - v ab) + 2 ab w: half 0 ab = A B, half 1 s = (A + B)(A + v B)
 BLS_HD Fp6 fp12_sqr_half_prod(const Fp12& a, bool h) {
   return fp6_mul(h ? fp6_add(a.c0, a.c1) : a.c0, h ? fp6_add(a.c0, fp6_mul_v(a.c1)) : a.c1);

@@ -60,6 +60,7 @@
 #include "bls/plan.hpp"
 #include "launchers.hpp"
 #include "kernels/curve_op_ids.hpp"
+#include "kernels/tower_op_ids.hpp"
 
 using namespace bls;
 
@@ -2651,6 +2652,77 @@ extern "C" int bls_gpu_curve_op_test(bls_gpu_ctx* ctx, uint32_t op, const uint32
   HIPC(ctx, hipMemcpyAsync(din, in, in_sz, hipMemcpyHostToDevice, s));
   HIPC(ctx, hipMemsetAsync(dout, 0, out_al + ws_sz, s));
   HIPC(ctx, launch_k_curve_op(op, din, n, dout, dws, s));
+  HIPC(ctx, hipMemcpyAsync(out, dout, out_sz, hipMemcpyDeviceToHost, s));
+  HIPC(ctx, hipStreamSynchronize(s));
+  return 0;
+}
+
+extern "C" int bls_gpu_tower_op_shape(uint32_t op, uint32_t* in_words, uint32_t* out_words) {
+  return tower_op_shape(op, in_words, out_words);
+}
+
+// TOP_MLQ_LINES: k_mlq<1> alone (launch_k_mlq_lines) on a zero-initialised PipeBufs that
+// holds only what mlq_lane reads -- chain (CH_RP, CH_HQ) and chain_live[i]; units_paired = 0,
+// so set_unit stays null -- and a zeroed line buffer.  Record: RP (x, y, z: Jacobian G1, any
+// z != 0), HQ (x.c0, x.c1, y.c0, y.c1); out: item k's 68 lines, event-major, each l0, l2, l3
+// as store_line wrote them (the buffer itself is line-major and lane-minor).
+static int tower_lines_test(bls_gpu_ctx* ctx, const uint32_t* in, uint32_t n, uint32_t* out) {
+  if (n > TOP_LINES_MAX) {
+    snprintf(ctx->err, sizeof(ctx->err), "tower op MLQ_LINES: %u items (at most %u)", n, TOP_LINES_MAX);
+    return -2;
+  }
+  const uint32_t iw = 12u * (uint32_t)tower_op_in_fps(TOP_MLQ_LINES), ow = 12u * (uint32_t)tower_op_out_fps(TOP_MLQ_LINES);
+  std::vector<uint32_t> chain((size_t)CHAIN_WORDS * 12 * n, 0u), live(n, 1u);
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint32_t* r = in + (size_t)iw * i;
+    uint32_t* row = chain.data() + (size_t)CHAIN_WORDS * 12 * i;
+    memcpy(row + 12 * CH_RP, r, 4 * 36);
+    memcpy(row + 12 * CH_HQ, r + 36, 4 * 48);
+  }
+  auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  const size_t words = mlq_line_words(n), stride = words / ow;
+  const size_t chain_sz = al(4 * chain.size()), w_sz = al(4ull * n), line_sz = al(4 * words);
+  if (ensure_dev(ctx, chain_sz + w_sz + line_sz)) return -1;
+  uint8_t* p = ctx->dev_ws;
+  PipeBufs b;
+  memset(&b, 0, sizeof(b));
+  b.n_sets = n;
+  b.chain = (Fp*)p;
+  b.chain_live = (uint32_t*)(p + chain_sz);
+  uint32_t* lines = (uint32_t*)(p + chain_sz + w_sz);
+  hipStream_t s = ctx->stream;
+  HIPC(ctx, hipMemcpyAsync(b.chain, chain.data(), 4 * chain.size(), hipMemcpyHostToDevice, s));
+  HIPC(ctx, hipMemcpyAsync(b.chain_live, live.data(), 4ull * n, hipMemcpyHostToDevice, s));
+  HIPC(ctx, hipMemsetAsync(lines, 0, line_sz, s));
+  HIPC(ctx, launch_k_mlq_lines(b, n, lines, s));
+  std::vector<uint32_t> buf(words);
+  HIPC(ctx, hipMemcpyAsync(buf.data(), lines, 4 * words, hipMemcpyDeviceToHost, s));
+  HIPC(ctx, hipStreamSynchronize(s));
+  for (uint32_t k = 0; k < n; ++k)
+    for (uint32_t ew = 0; ew < ow; ++ew) out[(size_t)ow * k + ew] = buf[(size_t)ew * stride + k];
+  return 0;
+}
+
+// One tower function per lane on Montgomery-form words (kernels/tower_ops.hpp): n records of
+// the op's in_words in, n of its out_words out.  An op in a flavour it does not exist in
+// returns -2 before anything is launched or written.
+extern "C" int bls_gpu_tower_op_test(bls_gpu_ctx* ctx, uint32_t op, const uint32_t* in, uint32_t n, uint32_t* out) {
+  CTX_LOCK(ctx);
+  HIPC(ctx, hipSetDevice(ctx->device));
+  uint32_t iw = 0, ow = 0;
+  if (tower_op_shape(op, &iw, &ow) != 0) {
+    snprintf(ctx->err, sizeof(ctx->err), "unknown tower op 0x%x", op);
+    return -2;
+  }
+  if (n == 0) return 0;
+  if ((op & ~TOP_D28_FLAG) == TOP_MLQ_LINES) return tower_lines_test(ctx, in, n, out);
+  const size_t in_sz = 4ull * iw * n, out_sz = 4ull * ow * n, in_al = (in_sz + 255) & ~(size_t)255;
+  if (ensure_dev(ctx, in_al + out_sz)) return -1;
+  uint32_t *din = (uint32_t*)ctx->dev_ws, *dout = (uint32_t*)(ctx->dev_ws + in_al);
+  hipStream_t s = ctx->stream;
+  HIPC(ctx, hipMemcpyAsync(din, in, in_sz, hipMemcpyHostToDevice, s));
+  HIPC(ctx, hipMemsetAsync(dout, 0, out_sz, s));
+  HIPC(ctx, launch_k_tower_op(op, din, n, dout, s));
   HIPC(ctx, hipMemcpyAsync(out, dout, out_sz, hipMemcpyDeviceToHost, s));
   HIPC(ctx, hipStreamSynchronize(s));
   return 0;

@@ -18,6 +18,7 @@
 #define BLS_FP_D28 1
 #include "../launchers.hpp"
 #include "bls/pairing.hpp"
+#include "tower_op_ids.hpp"
 
 using namespace bls;
 
@@ -156,5 +157,32 @@ hipError_t launch_k_chunk_simt(const PipeBufs& b, Fp12* save, hipStream_t s) {
 hipError_t launch_k_indiv_simt(const PipeBufs& b, const GroupBufs& g, Fp12* save, hipStream_t s) {
   if (b.n_indiv == 0) return hipSuccess;
   k_indiv_simt<<<bls_grid_for(b.n_indiv), BLS_BLOCK, 0, s>>>(b, g, save);
+  return hipGetLastError();
+}
+
+// Tower-op self-test (kernels/tower_ops.hpp), the ops whose functions are local to this file:
+// one lane per record calls mul12m, cyc_sqr or exp_x_m as fe_is_one does -- the second
+// operand of a product, and exp_x_m's base and result, in device memory -- on Fp12 values in
+// the words production holds them in.  k_chunk_simt's launch bounds and occupancy.
+__global__ __launch_bounds__(BLS_BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_tower_op_fin(
+    uint32_t op, const Fp12* in, uint32_t n, Fp12* out) {
+  const uint32_t i = blockIdx.x * BLS_BLOCK + threadIdx.x;
+  if (i >= n) return;
+  if (op == TOP_FIN_EXP_X_M) {
+    exp_x_m(in + i, out + i);
+    return;
+  }
+  if (op == TOP_FIN_CYC_SQR) {
+    out[i] = cyc_sqr(in[i]);
+    return;
+  }
+  const Fp12 a = in[2ull * i];
+  out[i] = op == TOP_FIN_MUL12M_CONJ ? mul12m<true>(a, in + 2ull * i + 1) : mul12m<false>(a, in + 2ull * i + 1);
+}
+
+hipError_t launch_k_tower_op_fin(uint32_t op, const Fp* in, uint32_t n, Fp* out, hipStream_t s) {
+  if (!tower_op_in_fin_tu(op)) return hipErrorInvalidValue;
+  k_tower_op_fin<<<bls_grid_for(n), BLS_BLOCK, 0, s>>>(op, reinterpret_cast<const Fp12*>(in), n,
+                                                      reinterpret_cast<Fp12*>(out));
   return hipGetLastError();
 }

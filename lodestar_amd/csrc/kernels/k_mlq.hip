@@ -33,6 +33,7 @@
 #include "bls/knobs.hpp"
 #include "bls/msm.hpp"
 #include "bls/pairing.hpp"
+#include "tower_op_ids.hpp"
 
 using namespace bls;
 
@@ -386,5 +387,45 @@ hipError_t launch_k_mlqf_msm(const PipeBufs& b, const MsmBufs& m, uint32_t group
   const uint32_t lanes = (count + per_lane - 1) / per_lane;
   k_mlf_msm<1><<<MSM_BUCKET_BLOCKS + bls_grid_for(lanes), BLS_BLOCK, 0, s>>>(b, m, count, n, groups, lines, stride,
                                                                             per_lane);
+  return hipGetLastError();
+}
+
+// k_mlq<1> alone over items [0, count), each its own: the line buffer of the tower-op
+// self-test's TOP_MLQ_LINES (bls_gpu.hip tower_lines_test)
+hipError_t launch_k_mlq_lines(const PipeBufs& b, uint32_t count, uint32_t* lines, hipStream_t s) {
+  if (count == 0) return hipSuccess;
+  const uint32_t stride = (count + BLS_BLOCK - 1) / BLS_BLOCK * BLS_BLOCK;
+  k_mlq<1><<<bls_grid_for(count), BLS_BLOCK, 0, s>>>(b, 0u, count, 0u, lines, stride, nullptr);
+  return hipGetLastError();
+}
+
+// Tower-op self-test (kernels/tower_ops.hpp), the ops whose functions are local to this file
+// or exist only in this flavour: one lane per record calls sqr12, mul_line12 or
+// fp12_mul_line2 as ml_f does; for the pair ops lanes 2k and 2k + 1 both load record k, each
+// runs its half with pair_swap as k_mlf2 does, and both write their result (2k, 2k + 1).
+// Both lanes of a pair take the same exit, and the lanes past the last record are idle as
+// k_mlf2's are.  k_mlf<1>'s launch bounds and occupancy; one wavefront per block (the Fp2
+// primitive's LDS slot).
+__global__ __launch_bounds__(BLS_BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1))) void k_tower_op_mlq(
+    uint32_t op, const Fp* in, uint32_t n, Fp12* out) {
+  const uint32_t t = blockIdx.x * BLS_BLOCK + threadIdx.x;
+  const bool pair = tower_op_is_pair(op);
+  const uint32_t k = pair ? t >> 1 : t;
+  const bool h = pair && (t & 1u) != 0u;
+  if (k >= n) return;
+  const Fp* r = in + (size_t)tower_op_in_fps(op) * k;
+  const Fp12 f = *reinterpret_cast<const Fp12*>(r);
+  const Fp2* l = reinterpret_cast<const Fp2*>(r + 12);
+  if (op == TOP_MLQ_SQR12) out[t] = sqr12(f);
+  else if (op == TOP_MLQ_MUL_LINE12) out[t] = mul_line12(f, l[0], l[1], l[2]);
+  else if (op == TOP_MLQ_MUL_LINE2) out[t] = fp12_mul_line2(f, l[0], l[1], l[2], l[3], l[4], l[5]);
+  else if (op == TOP_MLQ_SQR12_PAIR) out[t] = sqr12_pair(f, h);
+  else out[t] = mul_line12_pair(f, l[0], l[1], l[2], h);
+}
+
+hipError_t launch_k_tower_op_mlq(uint32_t op, const Fp* in, uint32_t n, Fp* out, hipStream_t s) {
+  if (!tower_op_in_mlq_tu(op)) return hipErrorInvalidValue;
+  const uint32_t lanes = tower_op_is_pair(op) ? 2u * n : n;
+  k_tower_op_mlq<<<bls_grid_for(lanes), BLS_BLOCK, 0, s>>>(op, in, n, reinterpret_cast<Fp12*>(out));
   return hipGetLastError();
 }

@@ -4,6 +4,7 @@
 #include "../launchers.hpp"
 #include "field_ops.hpp"
 #include "curve_ops.hpp"
+#include "tower_ops.hpp"
 
 using namespace bls;
 
@@ -67,4 +68,25 @@ hipError_t launch_k_curve_op(uint32_t op, const uint32_t* in, uint32_t n, uint32
   if (curve_op_in_chain_tu(base)) return launch_k_curve_op_chain(base, in, n, out, ws, s);
   if (op & COP_D28_FLAG) return launch_k_curve_op_d28(base, in, n, out, s);
   return curve_op_launch(base, in, n, out, s);
+}
+
+// the tower-op self-test (kernels/tower_ops.hpp): the 32-bit column flavour here, the
+// 28-bit-digit one in kernels/k_selftest_d28.hip, the file-local functions of
+// kernels/k_fin_simt.hip and kernels/k_mlq.hip beside the kernels that call them
+int tower_op_shape(uint32_t op, uint32_t* in_words, uint32_t* out_words) {
+  const uint32_t base = op & ~TOP_D28_FLAG;
+  if (base >= TOP_COUNT || !(tower_op_flavours(base) & ((op & TOP_D28_FLAG) ? 2u : 1u))) return -2;
+  if (in_words) *in_words = 12u * (uint32_t)tower_op_in_fps(base);
+  if (out_words) *out_words = 12u * (uint32_t)tower_op_out_fps(base);
+  return 0;
+}
+hipError_t launch_k_tower_op(uint32_t op, const uint32_t* in, uint32_t n, uint32_t* out, hipStream_t s) {
+  const uint32_t base = op & ~TOP_D28_FLAG;
+  if (tower_op_shape(op, nullptr, nullptr) != 0 || tower_op_on_host(base)) return hipErrorInvalidValue;
+  const Fp* fin = reinterpret_cast<const Fp*>(in);
+  Fp* fout = reinterpret_cast<Fp*>(out);
+  if (tower_op_in_fin_tu(base)) return launch_k_tower_op_fin(base, fin, n, fout, s);
+  if (tower_op_in_mlq_tu(base)) return launch_k_tower_op_mlq(base, fin, n, fout, s);
+  if (op & TOP_D28_FLAG) return launch_k_tower_op_d28(base, fin, n, fout, s);
+  return tower_op_launch(base, fin, n, fout, s);
 }

@@ -5,6 +5,7 @@
 #include "../launchers.hpp"
 #include "field_ops.hpp"
 #include "curve_ops.hpp"
+#include "tower_ops.hpp"
 
 using namespace bls;
 
@@ -14,4 +15,8 @@ hipError_t launch_k_field_op_d28(uint32_t op, const uint32_t* in, uint32_t n, ui
 
 hipError_t launch_k_curve_op_d28(uint32_t op, const uint32_t* in, uint32_t n, uint32_t* out, hipStream_t s) {
   return curve_op_launch(op, in, n, out, s);
+}
+
+hipError_t launch_k_tower_op_d28(uint32_t op, const Fp* in, uint32_t n, Fp* out, hipStream_t s) {
+  return tower_op_launch(op, in, n, out, s);
 }

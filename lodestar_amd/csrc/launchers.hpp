@@ -99,6 +99,17 @@ hipError_t launch_k_curve_op(uint32_t op, const uint32_t* in, uint32_t n, uint32
 hipError_t launch_k_curve_op_d28(uint32_t op, const uint32_t* in, uint32_t n, uint32_t* out, hipStream_t s);
 hipError_t launch_k_curve_op_chain(uint32_t op, const uint32_t* in, uint32_t n, uint32_t* out, void* ws,
                                    hipStream_t s);
+// tower-op self-test (kernels/tower_ops.hpp): op = base id | TOP_D28_FLAG; tower_op_shape:
+// record sizes in words, -2 for an unknown op or a flavour the op does not exist in.  The
+// _fin and _mlq launchers run the file-local functions of kernels/k_fin_simt.hip and
+// kernels/k_mlq.hip; launch_k_mlq_lines is k_mlq<1> alone over items [0, count), each its
+// own (launch_k_mlqf's first launch, units not paired)
+int tower_op_shape(uint32_t op, uint32_t* in_words, uint32_t* out_words);
+hipError_t launch_k_tower_op(uint32_t op, const uint32_t* in, uint32_t n, uint32_t* out, hipStream_t s);
+hipError_t launch_k_tower_op_d28(uint32_t op, const bls::Fp* in, uint32_t n, bls::Fp* out, hipStream_t s);
+hipError_t launch_k_tower_op_fin(uint32_t op, const bls::Fp* in, uint32_t n, bls::Fp* out, hipStream_t s);
+hipError_t launch_k_tower_op_mlq(uint32_t op, const bls::Fp* in, uint32_t n, bls::Fp* out, hipStream_t s);
+hipError_t launch_k_mlq_lines(const bls::PipeBufs& b, uint32_t count, uint32_t* lines, hipStream_t s);
 hipError_t launch_k_fpm_chain(bls::Fp* io, uint32_t lanes, uint32_t iters, hipStream_t s);
 size_t kernel_probe_out_bytes(const char* name);
 hipError_t launch_kernel_probe(const char* name, void* out, uint32_t lanes, hipStream_t s);

@@ -745,6 +745,26 @@ class GpuContext:
         self._check(self.lib.bls_gpu_curve_op_test(self._h, op, _ptr(rec), n, _ptr(out)), "bls_gpu_curve_op_test")
         return out[:n]
 
+    def tower_op_shape(self, op: int) -> tuple[int, int]:
+        """(words per input record, words per output record) of a tower-op self-test op"""
+        iw, ow = ctypes.c_uint32(), ctypes.c_uint32()
+        if self.lib.bls_gpu_tower_op_shape(op, ctypes.byref(iw), ctypes.byref(ow)) != 0:
+            raise NativeError(f"bls_gpu_tower_op_shape: unknown tower op {op:#x} (or not in this flavour)")
+        return iw.value, ow.value
+
+    def tower_op_test(self, op: int, records: np.ndarray) -> np.ndarray:
+        """One Fp6 / Fp12 tower function of the verify path per record on Montgomery-form words
+        (include/lodestar_bls.h bls_gpu_tower_op_test): records is (n, in_words) uint32, the
+        result (n, out_words)."""
+        iw, ow = self.tower_op_shape(op)
+        rec = np.ascontiguousarray(records, dtype=np.uint32)
+        if rec.ndim != 2 or rec.shape[1] != iw:
+            raise ValueError(f"tower op {op:#x} takes records of {iw} words, got {rec.shape}")
+        n = rec.shape[0]
+        out = np.zeros((max(n, 1), ow), dtype=np.uint32)
+        self._check(self.lib.bls_gpu_tower_op_test(self._h, op, _ptr(rec), n, _ptr(out)), "bls_gpu_tower_op_test")
+        return out[:n]
+
     def coop_run_test(self, name: str, frames: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
         """Program `name` of the loaded table run once per frame: frames is (n_frames,
         n_slots, 12) uint32 raw Fp limbs; returns the raw frames after the run and the

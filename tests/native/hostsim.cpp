@@ -226,6 +226,44 @@ void hs_fp12_mul_line2(const uint8_t* f, const uint8_t* l, const uint8_t* m, uin
                          rd_fp2(m + 192)),
           out);
 }
+// The Fp6 functions and the cyclotomic power on raw limbs in the device's memory layout
+// (Montgomery form in and out, 48 B little-endian per Fp; Fp6 = c0, c1, c2; Fp12 = c0, c1):
+// the records of tests/_towervec.py unchanged
+void hs_fp6_mul(const uint8_t* a, const uint8_t* b, uint8_t* out) {
+  Fp6 x, y;
+  memcpy(&x, a, sizeof(Fp6));
+  memcpy(&y, b, sizeof(Fp6));
+  const Fp6 r = fp6_mul(x, y);
+  memcpy(out, &r, sizeof(Fp6));
+}
+void hs_fp6_mul_01(const uint8_t* a, const uint8_t* d01, uint8_t* out) {
+  Fp6 x;
+  Fp2 d[2];
+  memcpy(&x, a, sizeof(Fp6));
+  memcpy(d, d01, sizeof(d));
+  const Fp6 r = fp6_mul_01(x, d[0], d[1]);
+  memcpy(out, &r, sizeof(Fp6));
+}
+void hs_fp6_mul_1(const uint8_t* a, const uint8_t* d1, uint8_t* out) {
+  Fp6 x;
+  Fp2 d;
+  memcpy(&x, a, sizeof(Fp6));
+  memcpy(&d, d1, sizeof(d));
+  const Fp6 r = fp6_mul_1(x, d);
+  memcpy(out, &r, sizeof(Fp6));
+}
+void hs_fp6_inv(const uint8_t* a, uint8_t* out) {
+  Fp6 x;
+  memcpy(&x, a, sizeof(Fp6));
+  const Fp6 r = fp6_inv(x);
+  memcpy(out, &r, sizeof(Fp6));
+}
+void hs_fp12_cyclotomic_exp_x(const uint8_t* a, uint8_t* out) {
+  Fp12 x;
+  memcpy(&x, a, sizeof(Fp12));
+  const Fp12 r = fp12_cyclotomic_exp_x(x);
+  memcpy(out, &r, sizeof(Fp12));
+}
 void hs_final_exp(const uint8_t* a, uint8_t* out) { wr_fp12(final_exponentiation(rd_fp12(a)), out); }
 // bls_gpu.hip verify_groups' decode of one failed chunk (bls/group_decode.hpp)
 int hs_group_decode(uint32_t m, uint32_t nbits, int whole_pass, const int32_t* v) {
