@@ -649,6 +649,19 @@ int bls_gpu_kernel_probe(bls_gpu_ctx* ctx, const char* name, uint32_t lanes, uin
 #define BLS_DEBUG_MSM_SERIAL 0x20000u
 int bls_gpu_set_debug_flags(bls_gpu_ctx* ctx, uint32_t flags);
 
+/* Test hook: the group-test rounds of the context's last verify pass (zero when it group-
+ * tested nothing; bls_stats does not say which round decided a failed chunk):
+ *   out[0] chunks group-tested (with a request of status OK)
+ *   out[1] ... whose whole value came from the failed chunk check's own final exponentiation
+ *   out[2] tests run in pass A        out[3] chunks decided by pass A's decode
+ *   out[4] tests run in pass B        out[5] chunks decided by pass B
+ *   out[6] tests run in pass C (= requests tested alone)
+ *   out[7] 1 when a chunk's pass A did not fit the group-sum workspace even on its own
+ *          (its requests went to pass C), else 0; chunks that do not fit together are
+ *          tested in several rounds, which the counters do not tell apart
+ * Returns 0, or -2 on a null argument. */
+int bls_gpu_group_test_counts(bls_gpu_ctx* ctx, uint32_t out[8]);
+
 #ifdef __cplusplus
 }
 #endif

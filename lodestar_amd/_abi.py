@@ -81,6 +81,7 @@ SYMBOLS = (
     "bls_gpu_coop_probe",
     "bls_gpu_kernel_probe",
     "bls_gpu_set_debug_flags",
+    "bls_gpu_group_test_counts",
     "bls_gpu_init_error",
     "bls_scratch_plan",
     "bls_gpu_admission",
@@ -348,6 +349,8 @@ def bind(lib: ctypes.CDLL) -> ctypes.CDLL:
         lib.bls_gpu_kernel_probe.restype = i32
         lib.bls_gpu_set_debug_flags.argtypes = [vp, u32]
         lib.bls_gpu_set_debug_flags.restype = i32
+        lib.bls_gpu_group_test_counts.argtypes = [vp, ctypes.POINTER(u32)]
+        lib.bls_gpu_group_test_counts.restype = i32
         lib.bls_gpu_init_error.argtypes = []
         lib.bls_gpu_init_error.restype = ctypes.c_char_p
         lib.bls_scratch_plan.argtypes = [u32, u32, u32, ctypes.POINTER(BlsAdmission)]

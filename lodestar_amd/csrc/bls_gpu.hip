@@ -94,6 +94,8 @@ struct bls_gpu_ctx {
   // [r] sig chains rather than the Pippenger sum (plan_pass: PassShape::use_msm), so a failure
   // there does not relaunch them (profiles/r05_ab_msm_min.json)
   bool last_merged_failed;
+  // the group-test rounds of the last pass (bls_gpu_group_test_counts; verify_groups)
+  uint32_t gt_counts[8];
   // grow-only device workspace and pinned staging
   uint32_t* msm_state;  // MSM bucket counters + tickets (MSM_STATE_WORDS), zero between passes
   uint8_t* dev_ws;
@@ -1710,8 +1712,8 @@ struct VerifyPass {
   // their requests' sets, paired ML(-g1, .) before k_group_coop.  Test g's sum lands in
   // virtual set indiv_vbase + n_direct + g (the group-tested requests' own slots, unused
   // under group sums; a pass never has more tests than group-tested requests).  Returns 0,
-  // 1 when the plan does not fit the workspace (the caller tests the requests alone), < 0
-  // on an error.
+  // 1 when the plan does not fit the workspace (nothing ran: group_rounds_ab), < 0 on an
+  // error.
   int group_sums(const std::vector<uint32_t>& goff, const std::vector<uint32_t>& gmem) {
     const uint32_t T = (uint32_t)(goff.size() - 1);
     if (iv.n_direct + T > iv.reqs.size()) return 1;
@@ -1748,6 +1750,7 @@ struct VerifyPass {
     return 0;
   }
 
+  int group_rounds_ab(const std::vector<GtChunk>& chunks, bool eq, std::vector<uint32_t>& alone);
   int verify_groups();
 
   // ---- stage: group tests over the failed chunks large enough for them
@@ -1789,25 +1792,37 @@ struct VerifyPass {
 // Group tests of the failed chunks iv.gt_chunks (the comment above group_test_min, bls/knobs.hpp): pass A
 // (bls/plan.hpp plan_group_tests_a), its decode (bls/group_decode.hpp, or pass B without
 // complement inference), pass C for what is left; verdicts into indiv_verdict.
-int VerifyPass::verify_groups() {
+//
+// Passes A and B over `chunks`; the requests left for pass C are appended to `alone`.
+// Returns 0, < 0 on an error, or 1 when pass A's group sums do not fit the workspace and
+// nothing ran: a bit group holds half its chunk's requests, so pass A sums ~nbits / 2 times
+// the chunk's sets, and the sum workspace holds the pass's n sets once -- a pass most of
+// whose sets sit in failed chunks does not fit in one round (the caller splits the chunks).
+// A single chunk that does not fit goes to pass C.
+int VerifyPass::group_rounds_ab(const std::vector<GtChunk>& chunks, bool eq, std::vector<uint32_t>& alone) {
   std::vector<int32_t>& verdict = indiv_verdict;
-  const bool eq = sh.gt_eq_mode != 0 && g.fe;
+  uint32_t* cnt = ctx->gt_counts;  // (bls_gpu_group_test_counts)
   GroupTestsA pa;
-  plan_group_tests_a(iv.gt_chunks, verdict.data(), eq, sh.gt_eq_mode != 2 && g.ref_fe, pa);
+  plan_group_tests_a(chunks, verdict.data(), eq, sh.gt_eq_mode != 2 && g.ref_fe, pa);
   std::vector<GroupTestChunk>& cs = pa.cs;
   if (!group_tests_fit(pa, sh.R, sh.n_chunks)) {
     snprintf(ctx->err, sizeof(ctx->err), "group-test plan exceeds its workspace");
     return -3;
   }
   std::vector<int32_t> gv;
-  std::vector<uint32_t> goff_b{0}, gmem_b, alone;  // alone: requests for pass C
+  std::vector<uint32_t> goff_b{0}, gmem_b;
   std::vector<size_t> in_b;
   const int rc_a = run_group_tests(pa.off, pa.members, gv, eq ? &pa.ref : nullptr);
   if (rc_a < 0) return -1;
-  if (rc_a == 1) {  // the group sums of pass A do not fit: every request alone
+  if (rc_a == 1 && chunks.size() > 1) return 1;
+  cnt[0] += (uint32_t)cs.size();
+  for (const GroupTestChunk& c : cs) cnt[1] += eq && !c.whole ? 1u : 0u;  // (ref = REF_CHUNK | chunk)
+  if (rc_a == 1) {  // the group sums of one chunk's pass A do not fit: its requests alone
+    cnt[7] = 1;
     for (const GroupTestChunk& c : cs) alone.insert(alone.end(), c.ok.begin(), c.ok.end());
-    cs.clear();
+    return 0;
   }
+  cnt[2] += (uint32_t)gv.size();
   // complement inference: with the test of all the chunk's requests (A) beside each bit
   // group G_j, FE(G_j) FE(rest_j) = FE(A) decides the complement too (FE(rest_j) == 1 iff
   // FE(G_j) == FE(A)), so a single invalid request b shows as exactly one failing test per
@@ -1825,6 +1840,7 @@ int VerifyPass::verify_groups() {
       continue;
     }
     for (uint32_t k = 0; k < m; ++k) verdict[c.ok[k]] = (int32_t)k == bad ? 0 : 1;
+    ++cnt[3];
   }
   if (eq) cs.clear();
   // decode pass A; plan pass B
@@ -1836,6 +1852,7 @@ int VerifyPass::verify_groups() {
       const bool pass = gv[idx++] == 1;
       if (pass || m == 1) {
         for (uint32_t t : c.ok) verdict[t] = pass ? 1 : 0;
+        ++cnt[3];
         continue;
       }
     }
@@ -1856,15 +1873,40 @@ int VerifyPass::verify_groups() {
   }
   const int rc_b = in_b.empty() ? 0 : run_group_tests(goff_b, gmem_b, gv);
   if (rc_b < 0) return -1;
+  if (!in_b.empty() && rc_b == 0) cnt[4] += (uint32_t)gv.size();
   for (size_t q = 0; q < in_b.size(); ++q) {
     GroupTestChunk& c = cs[in_b[q]];
     if (rc_b == 0 && gv[2 * q] == 0 && gv[2 * q + 1] == 1) {
       for (uint32_t k = 0; k < c.ok.size(); ++k) verdict[c.ok[k]] = (int32_t)k == c.b ? 0 : 1;
+      ++cnt[5];
     } else {
       alone.insert(alone.end(), c.ok.begin(), c.ok.end());
     }
   }
+  return 0;
+}
+
+int VerifyPass::verify_groups() {
+  std::vector<int32_t>& verdict = indiv_verdict;
+  const bool eq = sh.gt_eq_mode != 0 && g.fe;
+  std::vector<uint32_t> alone;  // requests for pass C
+  // passes A and B: every chunk in one round when its group sums fit (they do unless most
+  // of the pass failed), else the chunk list in halves until they do
+  std::vector<std::pair<size_t, size_t>> todo{{0, iv.gt_chunks.size()}};
+  while (!todo.empty()) {
+    const std::pair<size_t, size_t> part = todo.back();
+    todo.pop_back();
+    const std::vector<GtChunk> chunks(iv.gt_chunks.begin() + part.first, iv.gt_chunks.begin() + part.second);
+    const int rc = group_rounds_ab(chunks, eq, alone);
+    if (rc < 0) return rc;
+    if (rc == 1) {
+      const size_t mid = part.first + (part.second - part.first) / 2;
+      todo.push_back({mid, part.second});
+      todo.push_back({part.first, mid});
+    }
+  }
   // pass C: one test per request
+  std::vector<int32_t> gv;
   std::vector<uint32_t> goff_c{0};
   for (size_t k = 0; k < alone.size(); ++k) goff_c.push_back((uint32_t)k + 1);
   const int rc_c = run_group_tests(goff_c, alone, gv);
@@ -1873,11 +1915,13 @@ int VerifyPass::verify_groups() {
     snprintf(ctx->err, sizeof(ctx->err), "group tests: per-request sums do not fit");
     return -3;
   }
+  ctx->gt_counts[6] = (uint32_t)alone.size();
   for (size_t k = 0; k < alone.size(); ++k) verdict[alone[k]] = gv[k] == 1 ? 1 : 0;
   return 0;
 }
 
 int verify_body(bls_gpu_ctx* ctx, const bls_batch* in, const PassArgs& a) {
+  memset(ctx->gt_counts, 0, sizeof(ctx->gt_counts));
   HIPC(ctx, hipSetDevice(ctx->device));
   if (a.stats) memset(a.stats, 0, sizeof(*a.stats));
   if (in->n_reqs == 0) return 0;
@@ -2460,6 +2504,13 @@ int bls_gpu_sign(bls_gpu_ctx* ctx, const uint8_t* sks, const uint8_t* msgs, uint
 extern "C" int bls_gpu_set_debug_flags(bls_gpu_ctx* ctx, uint32_t flags) {
   if (!ctx) return -1;
   ctx->debug_flags = flags;
+  return 0;
+}
+
+extern "C" int bls_gpu_group_test_counts(bls_gpu_ctx* ctx, uint32_t out[8]) {
+  if (!ctx || !out) return -2;
+  CTX_LOCK(ctx);
+  memcpy(out, ctx->gt_counts, sizeof(ctx->gt_counts));
   return 0;
 }
 

@@ -694,6 +694,14 @@ class GpuContext:
         self._check(self.lib.bls_gpu_set_debug_flags(self._h, flags | self.base_debug_flags),
                     "bls_gpu_set_debug_flags")
 
+    def group_test_counts(self) -> list[int]:
+        """The group-test rounds of the last verify pass (bls_gpu_group_test_counts): chunks
+        group-tested, of those taking the whole's value from the chunk check, pass A's tests
+        and chunks decided, pass B's, pass C's tests, and whether pass A's sums did not fit."""
+        out = (ctypes.c_uint32 * 8)()
+        self._check(self.lib.bls_gpu_group_test_counts(self._h, out), "bls_gpu_group_test_counts")
+        return [int(x) for x in out]
+
     def mad_peak(self) -> tuple[float, float]:
         """Measured v_mad_u64_u32 rate (MAD/s) and the probe's duration (ms)."""
         rate, ms = ctypes.c_double(), ctypes.c_double()
