@@ -149,6 +149,12 @@ struct Carver {
     off += sizeof(T) * (count ? count : 1);
     return p;
   }
+  // take, with the element type read off the pointer it fills; chains: c.buf(a, n).buf(b, m)
+  template <class T>
+  Carver& buf(T*& p, size_t count) {
+    p = take<T>(count);
+    return *this;
+  }
 };
 
 int ensure_dev(bls_gpu_ctx* ctx, size_t bytes) {
@@ -160,6 +166,42 @@ int ensure_dev(bls_gpu_ctx* ctx, size_t bytes) {
   ctx->dev_ws_cap = cap;
   return 0;
 }
+
+// One single-launch device call: every entry point below that is no verify pass.  carve()
+// takes the call's layout once, as a function over a Carver: it runs without a base for the
+// size, grows the workspace, and runs again over it for the pointers.  From its construction
+// the object owns the tail of the stream: finish() is the call's one hipStreamSynchronize,
+// and every other way out (a failed copy or launch, an early return) waits in the destructor,
+// its result ignored so that the first error stays in ctx->err.  Nothing queued then outlives
+// the caller's buffers, the workspace or what was declared before the object: the host
+// vectors a queued copy reads or writes, and the table snapshot the kernels read.  The entry
+// point keeps the lock, hipSetDevice and its argument checks.
+struct OneShot {
+  bls_gpu_ctx* const ctx;
+  const hipStream_t s;
+  size_t bytes = 0;  // of the layout
+  bool done = false;
+  explicit OneShot(bls_gpu_ctx* c) : ctx(c), s(c->stream) {}
+  OneShot(const OneShot&) = delete;
+  ~OneShot() {
+    if (!done) (void)hipStreamSynchronize(s);
+  }
+  template <class Layout>
+  int carve(Layout&& layout) {
+    Carver size{nullptr, 0};
+    layout(size);
+    bytes = size.off;
+    if (ensure_dev(ctx, bytes)) return -1;
+    Carver at{ctx->dev_ws, 0};
+    layout(at);
+    return 0;
+  }
+  int finish() {
+    HIPC(ctx, hipStreamSynchronize(s));
+    done = true;
+    return 0;
+  }
+};
 
 // Pinned, device-mapped, coherent host memory: the kernels of a verify call read its
 // inputs from here and write its results here, so a call moves no data with copy or
@@ -273,14 +315,17 @@ static int load_coop_tables(bls_gpu_ctx* ctx) {
   }
   static_assert(sizeof(CoopOp) == 80, "CoopOp layout");
   // device copy: [ops | consts | the CoopEnv struct (filled at the end)]
-  size_t ops_bytes = (steps_bytes + 255) & ~(size_t)255;
-  const size_t env_off = (ops_bytes + (size_t)h.n_consts * sizeof(Fp) + 255) & ~(size_t)255;
-  HIPC(ctx, hipMalloc(&ctx->coop_dev, env_off + sizeof(CoopEnv)));
-  uint8_t* d = (uint8_t*)ctx->coop_dev;
-  HIPC(ctx, hipMemcpy(d, buf.data() + steps_off, steps_bytes, hipMemcpyHostToDevice));
-  HIPC(ctx, hipMemcpy(d + ops_bytes, buf.data() + consts_off, (size_t)h.n_consts * sizeof(Fp), hipMemcpyHostToDevice));
-  ctx->coop.ops = (const CoopOp*)d;
-  ctx->coop.consts = (const Fp*)(d + ops_bytes);
+  const auto layout = [&](Carver& c) {
+    c.buf(ctx->coop.ops, (size_t)h.n_steps * COOP_LANES).buf(ctx->coop.consts, h.n_consts).buf(ctx->coop.dev, 1);
+  };
+  Carver size{nullptr, 0};
+  layout(size);
+  HIPC(ctx, hipMalloc(&ctx->coop_dev, size.off));
+  Carver at{(uint8_t*)ctx->coop_dev, 0};
+  layout(at);
+  HIPC(ctx, hipMemcpy((void*)ctx->coop.ops, buf.data() + steps_off, steps_bytes, hipMemcpyHostToDevice));
+  HIPC(ctx, hipMemcpy((void*)ctx->coop.consts, buf.data() + consts_off, (size_t)h.n_consts * sizeof(Fp),
+                      hipMemcpyHostToDevice));
   ctx->coop.n_consts = h.n_consts;
   if (h.n_consts > COOP_MAX_CONSTS) {
     snprintf(ctx->err, sizeof(ctx->err), "%s: %u constants > %d", path.c_str(), h.n_consts, COOP_MAX_CONSTS);
@@ -351,7 +396,6 @@ static int load_coop_tables(bls_gpu_ctx* ctx) {
   }
   // kernels take the struct by pointer (its ~370 bytes by value, next to PipeBufs, made
   // the cooperative kernels' arguments ~830 bytes)
-  ctx->coop.dev = (const CoopEnv*)((uint8_t*)ctx->coop_dev + env_off);
   HIPC(ctx, hipMemcpy((void*)ctx->coop.dev, &ctx->coop, sizeof(CoopEnv), hipMemcpyHostToDevice));
   return 0;
 }
@@ -750,18 +794,15 @@ int64_t bls_gpu_load_pubkeys(bls_gpu_ctx* ctx, const uint8_t* pks, uint32_t n, u
   // all or nothing: a key that does not decode leaves the table as it was, so table
   // indices (validator indices) stay aligned across calls
   auto decode = [&](uint8_t* dst) -> int {
-    Carver cv{nullptr, 0};
-    cv.take<uint8_t>(in_bytes);
-    cv.take<int32_t>(n);
-    if (ensure_dev(ctx, cv.off) || ensure_host(ctx, cv.off)) return -2;
-    Carver c2{ctx->dev_ws, 0};
-    uint8_t* d_in = c2.take<uint8_t>(in_bytes);
-    int32_t* d_codes = c2.take<int32_t>(n);
     std::vector<int32_t> host_codes(n);
-    HIPC(ctx, hipMemcpyAsync(d_in, pks, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-    HIPC(ctx, launch_k_load_pubkeys(d_in, n, pk_len, (G1A*)dst, d_codes, ctx->stream));
-    HIPC(ctx, hipMemcpyAsync(host_codes.data(), d_codes, sizeof(int32_t) * n, hipMemcpyDeviceToHost, ctx->stream));
-    HIPC(ctx, hipStreamSynchronize(ctx->stream));
+    uint8_t* d_in = nullptr;
+    int32_t* d_codes = nullptr;
+    OneShot run(ctx);
+    if (run.carve([&](Carver& c) { c.buf(d_in, in_bytes).buf(d_codes, n); }) || ensure_host(ctx, run.bytes)) return -2;
+    HIPC(ctx, hipMemcpyAsync(d_in, pks, in_bytes, hipMemcpyHostToDevice, run.s));
+    HIPC(ctx, launch_k_load_pubkeys(d_in, n, pk_len, (G1A*)dst, d_codes, run.s));
+    HIPC(ctx, hipMemcpyAsync(host_codes.data(), d_codes, sizeof(int32_t) * n, hipMemcpyDeviceToHost, run.s));
+    if (run.finish()) return -1;
     if (codes) memcpy(codes, host_codes.data(), sizeof(int32_t) * n);
     for (uint32_t i = 0; i < n; ++i)
       if (host_codes[i] != 0) return 1;
@@ -842,18 +883,14 @@ int bls_gpu_validate_pubkeys(bls_gpu_ctx* ctx, const uint8_t* pks, uint32_t n, u
   if (n == 0) return 0;
   HIPC(ctx, hipSetDevice(ctx->device));
   const size_t in_bytes = (size_t)pk_len * n;
-  Carver cv{nullptr, 0};
-  cv.take<uint8_t>(in_bytes);
-  cv.take<int32_t>(n);
-  if (ensure_dev(ctx, cv.off)) return -1;
-  Carver c2{ctx->dev_ws, 0};
-  uint8_t* d_in = c2.take<uint8_t>(in_bytes);
-  int32_t* d_codes = c2.take<int32_t>(n);
-  HIPC(ctx, hipMemcpyAsync(d_in, pks, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-  HIPC(ctx, launch_k_validate_pubkeys(d_in, n, pk_len, d_codes, ctx->stream));
-  HIPC(ctx, hipMemcpyAsync(codes, d_codes, sizeof(int32_t) * n, hipMemcpyDeviceToHost, ctx->stream));
-  HIPC(ctx, hipStreamSynchronize(ctx->stream));
-  return 0;
+  uint8_t* d_in = nullptr;
+  int32_t* d_codes = nullptr;
+  OneShot run(ctx);
+  if (run.carve([&](Carver& c) { c.buf(d_in, in_bytes).buf(d_codes, n); })) return -1;
+  HIPC(ctx, hipMemcpyAsync(d_in, pks, in_bytes, hipMemcpyHostToDevice, run.s));
+  HIPC(ctx, launch_k_validate_pubkeys(d_in, n, pk_len, d_codes, run.s));
+  HIPC(ctx, hipMemcpyAsync(codes, d_codes, sizeof(int32_t) * n, hipMemcpyDeviceToHost, run.s));
+  return run.finish();
 }
 
 // ---------------------------------------------------------------------------
@@ -1948,20 +1985,17 @@ int verify_body(bls_gpu_ctx* ctx, const bls_batch* in, const PassArgs& a) {
 // One call under the context's lock.  A call that fails part-way may leave the MSM's
 // bucket counters / tickets (reset only by the kernels' last workgroups) mid-pass: they
 // are zeroed again before the context takes another call.
-static int verify_impl(bls_gpu_ctx* ctx, const bls_batch* in, int32_t* verdicts, bls_stats* stats,
-                       uint32_t scalar_base, uint8_t* partial_out, int32_t* partial_status,
-                       uint32_t* partial_err = nullptr, const std::vector<uint32_t>* req_bounds = nullptr,
-                       const SameMsgPlan* sm = nullptr, const bls_deposit_batch* dep = nullptr,
-                       const bls_committee_sets* cs = nullptr, const bls_span_sets* ss = nullptr) {
+// `a`: zero but for the entry point's own fields; a.pk is filled here.
+static int verify_impl(bls_gpu_ctx* ctx, const bls_batch* in, PassArgs a) {
   CTX_LOCK(ctx);
   ctx->wait_block = wait_blocks(knobs(), in->n_sets);
   // the table as this call sees it: kept until the stream is idle (every stage of a pass
   // that ran to its end has waited; one that failed part-way is waited for below), so a
   // load through another context never frees a buffer under this call's kernels
   PkView pk;
-  if (!dep) pk = pk_snapshot(ctx);
-  const int rc = verify_body(ctx, in, PassArgs{verdicts, stats, scalar_base, partial_out, partial_status, partial_err,
-                                               req_bounds, sm, dep, dep ? nullptr : &pk, cs, ss});
+  if (!a.dep) pk = pk_snapshot(ctx);
+  a.pk = a.dep ? nullptr : &pk;
+  const int rc = verify_body(ctx, in, a);
   if (rc != 0) (void)hipStreamSynchronize(ctx->stream);
   if (rc < 0 && ctx->msm_state) {
     (void)hipMemsetAsync(ctx->msm_state, 0, sizeof(uint32_t) * MSM_STATE_WORDS, ctx->stream);
@@ -1970,10 +2004,38 @@ static int verify_impl(bls_gpu_ctx* ctx, const bls_batch* in, int32_t* verdicts,
   return rc;
 }
 
+// The aggregate key of each of n_sets sets, as the three bls_gpu_aggregate_* calls return it.
+// The entry point's `inputs` carves the arrays it stages into b; its `front` copies them in
+// and launches its front kernel (the sets' sums into b.pk).  The vectors those copies read
+// are the entry point's, so they outlive the call's OneShot.  k_aggregate then serializes
+// every set (stage_pk skips the ones a front kernel summed).
+template <class Inputs, class Front>
+static int aggregate_sets(bls_gpu_ctx* ctx, uint32_t n_sets, uint8_t* out96, int32_t* codes, Inputs&& inputs,
+                          Front&& front) {
+  PipeBufs b;
+  memset(&b, 0, sizeof(b));
+  const PkView pk = pk_snapshot(ctx);  // dropped at return, after the stream's tail (run)
+  uint8_t* d_out = nullptr;
+  OneShot run(ctx);
+  if (run.carve([&](Carver& c) {
+        inputs(c, b);
+        c.buf(b.pk, n_sets).buf(b.pk_status, n_sets).buf(d_out, 96ull * n_sets);
+      }))
+    return -1;
+  b.n_sets = n_sets;
+  b.pk_table = pk.table();
+  b.pk_table_n = pk.snap.n;
+  if (const int rc = front(b, run.s)) return rc;
+  HIPC(ctx, launch_k_aggregate(b, d_out, run.s));
+  HIPC(ctx, hipMemcpyAsync(out96, d_out, 96ull * n_sets, hipMemcpyDeviceToHost, run.s));
+  if (codes) HIPC(ctx, hipMemcpyAsync(codes, b.pk_status, sizeof(int32_t) * n_sets, hipMemcpyDeviceToHost, run.s));
+  return run.finish();
+}
+
 extern "C" {
 
 int bls_gpu_verify(bls_gpu_ctx* ctx, const bls_batch* in, int32_t* verdicts, bls_stats* stats) {
-  return verify_impl(ctx, in, verdicts, stats, 0u, nullptr, nullptr);
+  return verify_impl(ctx, in, PassArgs{verdicts, stats});
 }
 
 int bls_gpu_verify_committees(bls_gpu_ctx* ctx, const bls_batch* in, const bls_committee_sets* cs, int32_t* verdicts,
@@ -1987,7 +2049,9 @@ int bls_gpu_verify_committees(bls_gpu_ctx* ctx, const bls_batch* in, const bls_c
     }
     if (const int rc = committee_check_sets(cs, in->n_sets, in->set_pk_offsets, ctx->err, sizeof(ctx->err))) return rc;
   }
-  return verify_impl(ctx, in, verdicts, stats, 0u, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, cs);
+  PassArgs a{verdicts, stats};
+  a.cs = cs;
+  return verify_impl(ctx, in, a);
 }
 
 int bls_gpu_verify_spans(bls_gpu_ctx* ctx, const bls_batch* in, const bls_span_sets* ss, int32_t* verdicts,
@@ -1997,7 +2061,9 @@ int bls_gpu_verify_spans(bls_gpu_ctx* ctx, const bls_batch* in, const bls_span_s
     CTX_LOCK(ctx);  // (for ctx->err; verify_impl takes the lock for the call itself)
     if (const int rc = span_check_sets(ss, in->n_sets, true, in->set_pk_offsets, ctx->err, sizeof(ctx->err))) return rc;
   }
-  return verify_impl(ctx, in, verdicts, stats, 0u, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, ss);
+  PassArgs a{verdicts, stats};
+  a.ss = ss;
+  return verify_impl(ctx, in, a);
 }
 
 int bls_gpu_verify_many(bls_gpu_ctx* ctx, const bls_batch* batches, uint32_t n_batches, int32_t* verdicts,
@@ -2005,7 +2071,7 @@ int bls_gpu_verify_many(bls_gpu_ctx* ctx, const bls_batch* batches, uint32_t n_b
   if (!ctx || (n_batches && (!batches || !verdicts))) return -2;
   if (stats) memset(stats, 0, sizeof(*stats));
   if (n_batches == 0) return 0;
-  if (n_batches == 1) return verify_impl(ctx, batches, verdicts, stats, 0u, nullptr, nullptr);
+  if (n_batches == 1) return verify_impl(ctx, batches, PassArgs{verdicts, stats});
   // messages with raw pubkeys keep their own pass: deserializeSet rejects a whole
   // message (worker.ts:43-46), which the merged pass does not track per message
   bool merge = true;
@@ -2014,7 +2080,7 @@ int bls_gpu_verify_many(bls_gpu_ctx* ctx, const bls_batch* batches, uint32_t n_b
     uint32_t off = 0;
     for (uint32_t k = 0; k < n_batches; ++k) {
       bls_stats st;
-      const int rc = verify_impl(ctx, &batches[k], verdicts + off, stats ? &st : nullptr, 0u, nullptr, nullptr);
+      const int rc = verify_impl(ctx, &batches[k], PassArgs{verdicts + off, stats ? &st : nullptr});
       if (rc != 0) return rc;
       off += batches[k].n_reqs;
       if (stats) {
@@ -2083,7 +2149,9 @@ int bls_gpu_verify_many(bls_gpu_ctx* ctx, const bls_batch* batches, uint32_t n_b
   all.signatures = sigs.data();
   all.signature_lens = lens ? sig_lens.data() : nullptr;
   all.seed = batches[0].seed;  // scalars: one random batch per pass (verdicts do not depend on them)
-  return verify_impl(ctx, &all, verdicts, stats, 0u, nullptr, nullptr, nullptr, &req_bounds);
+  PassArgs a{verdicts, stats};
+  a.req_bounds = &req_bounds;
+  return verify_impl(ctx, &all, a);
 }
 
 int bls_gpu_verify_same_message(bls_gpu_ctx* ctx, const bls_same_msg_batch* in, int32_t* set_verdicts,
@@ -2119,7 +2187,9 @@ int bls_gpu_verify_same_message(bls_gpu_ctx* ctx, const bls_same_msg_batch* in, 
   all.messages = msgs.data();
   all.signatures = in->signatures;
   all.seed = in->seed;
-  return verify_impl(ctx, &all, set_verdicts, stats, 0u, nullptr, nullptr, nullptr, nullptr, &sm);
+  PassArgs a{set_verdicts, stats};
+  a.sm = &sm;
+  return verify_impl(ctx, &all, a);
 }
 
 int bls_gpu_verify_deposits(bls_gpu_ctx* ctx, const bls_deposit_batch* in, int32_t* verdicts, bls_stats* stats) {
@@ -2138,7 +2208,9 @@ int bls_gpu_verify_deposits(bls_gpu_ctx* ctx, const bls_deposit_batch* in, int32
   DepositPlan dp;
   bls_batch all;
   plan_deposits(in, dp, all);
-  return verify_impl(ctx, &all, verdicts, stats, 0u, nullptr, nullptr, nullptr, nullptr, nullptr, in);
+  PassArgs a{verdicts, stats};
+  a.dep = in;
+  return verify_impl(ctx, &all, a);
 }
 
 int bls_gpu_partial(bls_gpu_ctx* ctx, const bls_batch* in, uint32_t set_index_base, uint8_t* out576,
@@ -2155,7 +2227,9 @@ int bls_gpu_partial(bls_gpu_ctx* ctx, const bls_batch* in, uint32_t set_index_ba
   }
   memset(out576, 0, 576);
   if (err_info) err_info[0] = 3, err_info[1] = 0;
-  return verify_impl(ctx, in, nullptr, stats, set_index_base, out576, status, err_info);
+  PassArgs a{nullptr, stats, set_index_base};
+  a.partial_out = out576, a.partial_status = status, a.partial_err = err_info;
+  return verify_impl(ctx, in, a);
 }
 
 int bls_gpu_final_check(bls_gpu_ctx* ctx, const uint8_t* partials, uint32_t n, int32_t* verdict) {
@@ -2163,22 +2237,14 @@ int bls_gpu_final_check(bls_gpu_ctx* ctx, const uint8_t* partials, uint32_t n, i
   HIPC(ctx, hipSetDevice(ctx->device));
   if (!partials || !verdict || n == 0) return -2;
   const uint32_t lvl1 = (n + FPROD_FAN - 1) / FPROD_FAN;
-  Carver c{nullptr, 0};
-  c.take<Fp12>(n);
-  c.take<Fp12>(lvl1);
-  c.take<Fp12>(lvl1);
-  c.take<int32_t>(1);
-  if (ensure_dev(ctx, c.off)) return -1;
-  Carver d{ctx->dev_ws, 0};
-  Fp12* in = d.take<Fp12>(n);
-  Fp12* t[2] = {d.take<Fp12>(lvl1), d.take<Fp12>(lvl1)};
-  int32_t* dv = d.take<int32_t>(1);
-  hipStream_t s = ctx->stream;
-  HIPC(ctx, hipMemcpyAsync(in, partials, 576ull * n, hipMemcpyHostToDevice, s));
-  if (fprod_tree(ctx, in, n, t, dv, nullptr, s)) return -1;
-  HIPC(ctx, hipMemcpyAsync(verdict, dv, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-  HIPC(ctx, hipStreamSynchronize(s));
-  return 0;
+  Fp12 *in = nullptr, *t[2] = {nullptr, nullptr};
+  int32_t* dv = nullptr;
+  OneShot run(ctx);
+  if (run.carve([&](Carver& c) { c.buf(in, n).buf(t[0], lvl1).buf(t[1], lvl1).buf(dv, 1); })) return -1;
+  HIPC(ctx, hipMemcpyAsync(in, partials, 576ull * n, hipMemcpyHostToDevice, run.s));
+  if (fprod_tree(ctx, in, n, t, dv, nullptr, run.s)) return -1;
+  HIPC(ctx, hipMemcpyAsync(verdict, dv, sizeof(int32_t), hipMemcpyDeviceToHost, run.s));
+  return run.finish();
 }
 
 int bls_gpu_aggregate_pubkeys(bls_gpu_ctx* ctx, const uint32_t* set_pk_offsets, const uint32_t* pk_indices,
@@ -2190,52 +2256,24 @@ int bls_gpu_aggregate_pubkeys(bls_gpu_ctx* ctx, const uint32_t* set_pk_offsets, 
   std::vector<uint32_t> agg_list;
   for (uint32_t i = 0; i < n_sets; ++i)
     if (set_pk_offsets[i + 1] - set_pk_offsets[i] >= BLS_AGG_WAVE_MIN) agg_list.push_back(i);
-  PipeBufs b;
-  memset(&b, 0, sizeof(b));
-  auto carve = [&](Carver& c, uint8_t*& d_out) {
-    b.set_pk_off = c.take<uint32_t>(n_sets + 1);
-    b.pk_idx = c.take<uint32_t>(n_idx);
-    b.agg_sets = c.take<uint32_t>(agg_list.size());
-    b.pk = c.take<G1J>(n_sets);
-    b.pk_status = c.take<int32_t>(n_sets);
-    d_out = c.take<uint8_t>(96ull * n_sets);
-  };
-  uint8_t* d_out = nullptr;
-  {
-    Carver c{nullptr, 0};
-    carve(c, d_out);
-    if (ensure_dev(ctx, c.off)) return -1;
-  }
-  Carver c{ctx->dev_ws, 0};
-  carve(c, d_out);
-  b.n_sets = n_sets;
-  const PkView pk = pk_snapshot(ctx);  // dropped at return; an error path waits first (below)
-  b.pk_table = pk.table();
-  b.pk_table_n = pk.snap.n;
-  hipStream_t s = ctx->stream;
-  struct Drain {  // a failed copy or launch leaves earlier kernels on the stream
-    hipStream_t s;
-    bool armed;
-    ~Drain() {
-      if (armed) (void)hipStreamSynchronize(s);
-    }
-  } drain{s, true};
-  HIPC(ctx, hipMemcpyAsync((void*)b.set_pk_off, set_pk_offsets, sizeof(uint32_t) * (n_sets + 1),
-                           hipMemcpyHostToDevice, s));
-  HIPC(ctx, hipMemcpyAsync((void*)b.pk_idx, pk_indices, sizeof(uint32_t) * n_idx, hipMemcpyHostToDevice, s));
-  b.n_agg = (uint32_t)agg_list.size();
-  b.agg_min = agg_list.empty() ? 0u : BLS_AGG_WAVE_MIN;
-  if (!agg_list.empty()) {
-    HIPC(ctx, hipMemcpyAsync((void*)b.agg_sets, agg_list.data(), sizeof(uint32_t) * agg_list.size(),
-                             hipMemcpyHostToDevice, s));
-    HIPC(ctx, launch_k_pk_agg(b, s));  // the big aggregates first; k_aggregate serializes every set
-  }
-  HIPC(ctx, launch_k_aggregate(b, d_out, s));
-  HIPC(ctx, hipMemcpyAsync(out96, d_out, 96ull * n_sets, hipMemcpyDeviceToHost, s));
-  if (codes) HIPC(ctx, hipMemcpyAsync(codes, b.pk_status, sizeof(int32_t) * n_sets, hipMemcpyDeviceToHost, s));
-  HIPC(ctx, hipStreamSynchronize(s));
-  drain.armed = false;
-  return 0;
+  return aggregate_sets(
+      ctx, n_sets, out96, codes,
+      [&](Carver& c, PipeBufs& b) {
+        c.buf(b.set_pk_off, n_sets + 1).buf(b.pk_idx, n_idx).buf(b.agg_sets, agg_list.size());
+      },
+      [&](PipeBufs& b, hipStream_t s) -> int {
+        HIPC(ctx, hipMemcpyAsync((void*)b.set_pk_off, set_pk_offsets, sizeof(uint32_t) * (n_sets + 1),
+                                 hipMemcpyHostToDevice, s));
+        HIPC(ctx, hipMemcpyAsync((void*)b.pk_idx, pk_indices, sizeof(uint32_t) * n_idx, hipMemcpyHostToDevice, s));
+        b.n_agg = (uint32_t)agg_list.size();
+        b.agg_min = agg_list.empty() ? 0u : BLS_AGG_WAVE_MIN;
+        if (!agg_list.empty()) {
+          HIPC(ctx, hipMemcpyAsync((void*)b.agg_sets, agg_list.data(), sizeof(uint32_t) * agg_list.size(),
+                                   hipMemcpyHostToDevice, s));
+          HIPC(ctx, launch_k_pk_agg(b, s));  // the big aggregates first; k_aggregate serializes every set
+        }
+        return 0;
+      });
 }
 
 int bls_gpu_aggregate_committee_bits(bls_gpu_ctx* ctx, const bls_committee_sets* cs, uint32_t n_sets, uint8_t* out96,
@@ -2252,52 +2290,25 @@ int bls_gpu_aggregate_committee_bits(bls_gpu_ctx* ctx, const bls_committee_sets*
   HIPC(ctx, hipSetDevice(ctx->device));
   if (n_sets == 0) return 0;
   const uint32_t n_bytes = cs->set_bits_off[n_sets];
-  PipeBufs b;
-  memset(&b, 0, sizeof(b));
-  auto carve = [&](Carver& c, uint8_t*& d_out) {
-    b.set_committee = c.take<uint32_t>(n_sets);
-    b.set_bits_off = c.take<uint32_t>(n_sets + 1);
-    b.bits = c.take<uint8_t>(n_bytes);
-    b.bits_sets = c.take<uint32_t>(n_sets);
-    b.pk = c.take<G1J>(n_sets);
-    b.pk_status = c.take<int32_t>(n_sets);
-    d_out = c.take<uint8_t>(96ull * n_sets);
-  };
-  uint8_t* d_out = nullptr;
-  {
-    Carver c{nullptr, 0};
-    carve(c, d_out);
-    if (ensure_dev(ctx, c.off)) return -1;
-  }
-  Carver c{ctx->dev_ws, 0};
-  carve(c, d_out);
-  b.n_sets = b.n_bits = n_sets;
-  b.cm_groups = ctx->cm_dev;
-  const PkView pk = pk_snapshot(ctx);  // dropped at return; an error path waits first (below)
-  b.pk_table = pk.table();
-  b.pk_table_n = pk.snap.n;
   std::vector<uint32_t> all(n_sets);
   for (uint32_t i = 0; i < n_sets; ++i) all[i] = i;
-  hipStream_t s = ctx->stream;
-  struct Drain {  // a failed copy or launch leaves earlier kernels on the stream
-    hipStream_t s;
-    bool armed;
-    ~Drain() {
-      if (armed) (void)hipStreamSynchronize(s);
-    }
-  } drain{s, true};
-  HIPC(ctx, hipMemcpyAsync((void*)b.set_committee, cs->set_committee, sizeof(uint32_t) * n_sets, hipMemcpyHostToDevice, s));
-  HIPC(ctx, hipMemcpyAsync((void*)b.set_bits_off, cs->set_bits_off, sizeof(uint32_t) * (n_sets + 1),
-                           hipMemcpyHostToDevice, s));
-  if (n_bytes) HIPC(ctx, hipMemcpyAsync((void*)b.bits, cs->bits, n_bytes, hipMemcpyHostToDevice, s));
-  HIPC(ctx, hipMemcpyAsync((void*)b.bits_sets, all.data(), sizeof(uint32_t) * n_sets, hipMemcpyHostToDevice, s));
-  HIPC(ctx, launch_k_pk_bits(b, s));
-  HIPC(ctx, launch_k_aggregate(b, d_out, s));  // stage_pk skips every set; it serializes them
-  HIPC(ctx, hipMemcpyAsync(out96, d_out, 96ull * n_sets, hipMemcpyDeviceToHost, s));
-  if (codes) HIPC(ctx, hipMemcpyAsync(codes, b.pk_status, sizeof(int32_t) * n_sets, hipMemcpyDeviceToHost, s));
-  HIPC(ctx, hipStreamSynchronize(s));
-  drain.armed = false;
-  return 0;
+  return aggregate_sets(
+      ctx, n_sets, out96, codes,
+      [&](Carver& c, PipeBufs& b) {
+        c.buf(b.set_committee, n_sets).buf(b.set_bits_off, n_sets + 1).buf(b.bits, n_bytes).buf(b.bits_sets, n_sets);
+      },
+      [&](PipeBufs& b, hipStream_t s) -> int {
+        b.n_bits = n_sets;
+        b.cm_groups = ctx->cm_dev;
+        HIPC(ctx, hipMemcpyAsync((void*)b.set_committee, cs->set_committee, sizeof(uint32_t) * n_sets,
+                                 hipMemcpyHostToDevice, s));
+        HIPC(ctx, hipMemcpyAsync((void*)b.set_bits_off, cs->set_bits_off, sizeof(uint32_t) * (n_sets + 1),
+                                 hipMemcpyHostToDevice, s));
+        if (n_bytes) HIPC(ctx, hipMemcpyAsync((void*)b.bits, cs->bits, n_bytes, hipMemcpyHostToDevice, s));
+        HIPC(ctx, hipMemcpyAsync((void*)b.bits_sets, all.data(), sizeof(uint32_t) * n_sets, hipMemcpyHostToDevice, s));
+        HIPC(ctx, launch_k_pk_bits(b, s));
+        return 0;
+      });
 }
 
 int bls_gpu_aggregate_spans(bls_gpu_ctx* ctx, const bls_span_sets* ss, uint32_t n_sets, uint8_t* out96,
@@ -2312,68 +2323,37 @@ int bls_gpu_aggregate_spans(bls_gpu_ctx* ctx, const bls_span_sets* ss, uint32_t 
   HIPC(ctx, hipSetDevice(ctx->device));
   if (n_sets == 0) return 0;
   const uint32_t n_refs = ss->set_span_off[n_sets], n_bytes = ss->set_bits_off[n_sets];
-  PipeBufs b;
-  memset(&b, 0, sizeof(b));
-  auto carve = [&](Carver& c, uint8_t*& d_out) {
-    b.set_span_off = c.take<uint32_t>(n_sets + 1);
-    b.span_refs = c.take<uint32_t>(n_refs);
-    b.set_bits_off = c.take<uint32_t>(n_sets + 1);
-    b.bits = c.take<uint8_t>(n_bytes);
-    b.span_sets = c.take<uint32_t>(n_sets);
-    b.pk = c.take<G1J>(n_sets);
-    b.pk_status = c.take<int32_t>(n_sets);
-    d_out = c.take<uint8_t>(96ull * n_sets);
-  };
-  uint8_t* d_out = nullptr;
-  {
-    Carver c{nullptr, 0};
-    carve(c, d_out);
-    if (ensure_dev(ctx, c.off)) return -1;
-  }
-  Carver c{ctx->dev_ws, 0};
-  carve(c, d_out);
-  b.n_sets = b.n_span = n_sets;
-  b.cm_groups = ctx->cm_dev;
-  const PkView pk = pk_snapshot(ctx);  // dropped at return; an error path waits first (below)
-  b.pk_table = pk.table();
-  b.pk_table_n = pk.snap.n;
   std::vector<uint32_t> all(n_sets);
   for (uint32_t i = 0; i < n_sets; ++i) all[i] = i;
-  hipStream_t s = ctx->stream;
-  struct Drain {  // a failed copy or launch leaves earlier kernels on the stream
-    hipStream_t s;
-    bool armed;
-    ~Drain() {
-      if (armed) (void)hipStreamSynchronize(s);
-    }
-  } drain{s, true};
-  HIPC(ctx, hipMemcpyAsync((void*)b.set_span_off, ss->set_span_off, sizeof(uint32_t) * (n_sets + 1),
-                           hipMemcpyHostToDevice, s));
-  HIPC(ctx, hipMemcpyAsync((void*)b.span_refs, ss->span_refs, sizeof(uint32_t) * n_refs, hipMemcpyHostToDevice, s));
-  HIPC(ctx, hipMemcpyAsync((void*)b.set_bits_off, ss->set_bits_off, sizeof(uint32_t) * (n_sets + 1),
-                           hipMemcpyHostToDevice, s));
-  if (n_bytes) HIPC(ctx, hipMemcpyAsync((void*)b.bits, ss->bits, n_bytes, hipMemcpyHostToDevice, s));
-  HIPC(ctx, hipMemcpyAsync((void*)b.span_sets, all.data(), sizeof(uint32_t) * n_sets, hipMemcpyHostToDevice, s));
-  HIPC(ctx, launch_k_pk_span(b, s));
-  HIPC(ctx, launch_k_aggregate(b, d_out, s));  // stage_pk skips every set; it serializes them
-  HIPC(ctx, hipMemcpyAsync(out96, d_out, 96ull * n_sets, hipMemcpyDeviceToHost, s));
-  if (codes) HIPC(ctx, hipMemcpyAsync(codes, b.pk_status, sizeof(int32_t) * n_sets, hipMemcpyDeviceToHost, s));
-  HIPC(ctx, hipStreamSynchronize(s));
-  drain.armed = false;
-  return 0;
+  return aggregate_sets(
+      ctx, n_sets, out96, codes,
+      [&](Carver& c, PipeBufs& b) {
+        c.buf(b.set_span_off, n_sets + 1).buf(b.span_refs, n_refs).buf(b.set_bits_off, n_sets + 1);
+        c.buf(b.bits, n_bytes).buf(b.span_sets, n_sets);
+      },
+      [&](PipeBufs& b, hipStream_t s) -> int {
+        b.n_span = n_sets;
+        b.cm_groups = ctx->cm_dev;
+        HIPC(ctx, hipMemcpyAsync((void*)b.set_span_off, ss->set_span_off, sizeof(uint32_t) * (n_sets + 1),
+                                 hipMemcpyHostToDevice, s));
+        HIPC(ctx, hipMemcpyAsync((void*)b.span_refs, ss->span_refs, sizeof(uint32_t) * n_refs, hipMemcpyHostToDevice, s));
+        HIPC(ctx, hipMemcpyAsync((void*)b.set_bits_off, ss->set_bits_off, sizeof(uint32_t) * (n_sets + 1),
+                                 hipMemcpyHostToDevice, s));
+        if (n_bytes) HIPC(ctx, hipMemcpyAsync((void*)b.bits, ss->bits, n_bytes, hipMemcpyHostToDevice, s));
+        HIPC(ctx, hipMemcpyAsync((void*)b.span_sets, all.data(), sizeof(uint32_t) * n_sets, hipMemcpyHostToDevice, s));
+        HIPC(ctx, launch_k_pk_span(b, s));
+        return 0;
+      });
 }
 
 static int run_simple(bls_gpu_ctx* ctx, uint32_t n, size_t in_a, const void* a, size_t in_b, const void* bsrc,
                       size_t out_per, void* out, int which) {
   HIPC(ctx, hipSetDevice(ctx->device));
   if (n == 0) return 0;
-  size_t need = ((in_a * n + 255) & ~(size_t)255) + ((in_b * n + 255) & ~(size_t)255) + out_per * n + 256;
-  if (ensure_dev(ctx, need)) return -1;
-  Carver c{ctx->dev_ws, 0};
-  uint8_t* d_a = c.take<uint8_t>(in_a * n);
-  uint8_t* d_b = c.take<uint8_t>(in_b ? in_b * n : 1);
-  uint8_t* d_o = c.take<uint8_t>(out_per * n);
-  hipStream_t s = ctx->stream;
+  uint8_t *d_a = nullptr, *d_b = nullptr, *d_o = nullptr;
+  OneShot run(ctx);
+  if (run.carve([&](Carver& c) { c.buf(d_a, in_a * n).buf(d_b, in_b * n).buf(d_o, out_per * n); })) return -1;
+  const hipStream_t s = run.s;
   HIPC(ctx, hipMemcpyAsync(d_a, a, in_a * n, hipMemcpyHostToDevice, s));
   if (in_b) HIPC(ctx, hipMemcpyAsync(d_b, bsrc, in_b * n, hipMemcpyHostToDevice, s));
   switch (which) {
@@ -2382,8 +2362,7 @@ static int run_simple(bls_gpu_ctx* ctx, uint32_t n, size_t in_a, const void* a, 
     default: HIPC(ctx, launch_k_sign(d_a, d_b, n, d_o, s)); break;
   }
   HIPC(ctx, hipMemcpyAsync(out, d_o, out_per * n, hipMemcpyDeviceToHost, s));
-  HIPC(ctx, hipStreamSynchronize(s));
-  return 0;
+  return run.finish();
 }
 
 int bls_gpu_aggregate_signatures(bls_gpu_ctx* ctx, const uint8_t* sigs96, const uint32_t* list_offsets,
@@ -2400,34 +2379,23 @@ int bls_gpu_aggregate_signatures(bls_gpu_ctx* ctx, const uint8_t* sigs96, const 
       return -2;
     }
   if (n > 0 && !sigs96) return -2;
-  auto carve = [&](Carver& c, uint8_t*& d_in, uint32_t*& d_off, G2A*& d_pts, int32_t*& d_sc, uint8_t*& d_out,
-                   int32_t*& d_codes) {
-    d_in = c.take<uint8_t>(96ull * n);
-    d_off = c.take<uint32_t>(n_lists + 1);
-    d_pts = c.take<G2A>(n);
-    d_sc = c.take<int32_t>(n);
-    d_out = c.take<uint8_t>(96ull * n_lists);
-    d_codes = c.take<int32_t>(n_lists);
-  };
-  uint8_t *d_in, *d_out;
-  uint32_t* d_off;
-  G2A* d_pts;
-  int32_t *d_sc, *d_codes;
-  {
-    Carver c{nullptr, 0};
-    carve(c, d_in, d_off, d_pts, d_sc, d_out, d_codes);
-    if (ensure_dev(ctx, c.off)) return -1;
-  }
-  Carver c{ctx->dev_ws, 0};
-  carve(c, d_in, d_off, d_pts, d_sc, d_out, d_codes);
-  hipStream_t s = ctx->stream;
+  uint8_t *d_in = nullptr, *d_out = nullptr;
+  uint32_t* d_off = nullptr;
+  G2A* d_pts = nullptr;
+  int32_t *d_sc = nullptr, *d_codes = nullptr;
+  OneShot run(ctx);
+  if (run.carve([&](Carver& c) {
+        c.buf(d_in, 96ull * n).buf(d_off, n_lists + 1).buf(d_pts, n).buf(d_sc, n);
+        c.buf(d_out, 96ull * n_lists).buf(d_codes, n_lists);
+      }))
+    return -1;
+  const hipStream_t s = run.s;
   if (n) HIPC(ctx, hipMemcpyAsync(d_in, sigs96, 96ull * n, hipMemcpyHostToDevice, s));
   HIPC(ctx, hipMemcpyAsync(d_off, list_offsets, sizeof(uint32_t) * (n_lists + 1), hipMemcpyHostToDevice, s));
   HIPC(ctx, launch_k_sig_aggregate(d_in, n, d_off, n_lists, d_pts, d_sc, d_out, d_codes, s));
   HIPC(ctx, hipMemcpyAsync(out96, d_out, 96ull * n_lists, hipMemcpyDeviceToHost, s));
   HIPC(ctx, hipMemcpyAsync(codes, d_codes, sizeof(int32_t) * n_lists, hipMemcpyDeviceToHost, s));
-  HIPC(ctx, hipStreamSynchronize(s));
-  return 0;
+  return run.finish();
 }
 
 int bls_gpu_g2_decompress(bls_gpu_ctx* ctx, const uint8_t* in96, uint32_t n, int validate, uint8_t* out192,
@@ -2436,22 +2404,16 @@ int bls_gpu_g2_decompress(bls_gpu_ctx* ctx, const uint8_t* in96, uint32_t n, int
   HIPC(ctx, hipSetDevice(ctx->device));
   if (n == 0) return 0;
   if (!in96 || !out192 || !codes) return -2;
-  Carver cv{nullptr, 0};
-  cv.take<uint8_t>(96ull * n);
-  cv.take<uint8_t>(192ull * n);
-  cv.take<int32_t>(n);
-  if (ensure_dev(ctx, cv.off)) return -1;
-  Carver c{ctx->dev_ws, 0};
-  uint8_t* d_in = c.take<uint8_t>(96ull * n);
-  uint8_t* d_out = c.take<uint8_t>(192ull * n);
-  int32_t* d_codes = c.take<int32_t>(n);
-  hipStream_t s = ctx->stream;
+  uint8_t *d_in = nullptr, *d_out = nullptr;
+  int32_t* d_codes = nullptr;
+  OneShot run(ctx);
+  if (run.carve([&](Carver& c) { c.buf(d_in, 96ull * n).buf(d_out, 192ull * n).buf(d_codes, n); })) return -1;
+  const hipStream_t s = run.s;
   HIPC(ctx, hipMemcpyAsync(d_in, in96, 96ull * n, hipMemcpyHostToDevice, s));
   HIPC(ctx, launch_k_g2_decompress(d_in, n, validate, d_out, d_codes, s));
   HIPC(ctx, hipMemcpyAsync(out192, d_out, 192ull * n, hipMemcpyDeviceToHost, s));
   HIPC(ctx, hipMemcpyAsync(codes, d_codes, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));
-  HIPC(ctx, hipStreamSynchronize(s));
-  return 0;
+  return run.finish();
 }
 
 int bls_gpu_ssz_roots(bls_gpu_ctx* ctx, uint32_t kind, const uint8_t* objs, uint32_t n, const uint8_t* domains,
@@ -2466,22 +2428,15 @@ int bls_gpu_ssz_roots(bls_gpu_ctx* ctx, uint32_t kind, const uint8_t* objs, uint
   if (n == 0) return 0;
   if (!objs || !out32) return -2;
   const size_t obj_bytes = (size_t)BLS_SSZ_SIZE(kind) * n, dom_bytes = domains ? (domain_stride ? 32ull * n : 32) : 0;
-  Carver cv{nullptr, 0};
-  cv.take<uint8_t>(obj_bytes);
-  cv.take<uint8_t>(dom_bytes);
-  cv.take<uint8_t>(32ull * n);
-  if (ensure_dev(ctx, cv.off)) return -1;
-  Carver c{ctx->dev_ws, 0};
-  uint8_t* d_obj = c.take<uint8_t>(obj_bytes);
-  uint8_t* d_dom = c.take<uint8_t>(dom_bytes);
-  uint8_t* d_out = c.take<uint8_t>(32ull * n);
-  hipStream_t s = ctx->stream;
+  uint8_t *d_obj = nullptr, *d_dom = nullptr, *d_out = nullptr;
+  OneShot run(ctx);
+  if (run.carve([&](Carver& c) { c.buf(d_obj, obj_bytes).buf(d_dom, dom_bytes).buf(d_out, 32ull * n); })) return -1;
+  const hipStream_t s = run.s;
   HIPC(ctx, hipMemcpyAsync(d_obj, objs, obj_bytes, hipMemcpyHostToDevice, s));
   if (domains) HIPC(ctx, hipMemcpyAsync(d_dom, domains, dom_bytes, hipMemcpyHostToDevice, s));
   HIPC(ctx, launch_k_ssz_roots(kind, d_obj, n, domains ? d_dom : nullptr, domain_stride, d_out, s));
   HIPC(ctx, hipMemcpyAsync(out32, d_out, 32ull * n, hipMemcpyDeviceToHost, s));
-  HIPC(ctx, hipStreamSynchronize(s));
-  return 0;
+  return run.finish();
 }
 
 int bls_gpu_hash_to_g2(bls_gpu_ctx* ctx, const uint8_t* msgs, uint32_t n, uint8_t* out192) {
@@ -2520,14 +2475,15 @@ extern "C" int bls_gpu_mad_peak(bls_gpu_ctx* ctx, double* mads_per_s, double* ms
   int cus = 0;
   HIPC(ctx, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
   const uint32_t blocks = (uint32_t)cus * 8, iters = 1024;
-  if (ensure_dev(ctx, sizeof(uint64_t) * blocks)) return -1;
-  uint64_t* d = (uint64_t*)ctx->dev_ws;
-  hipStream_t s = ctx->stream;
+  uint64_t* d = nullptr;
+  OneShot run(ctx);
+  if (run.carve([&](Carver& c) { d = c.take<uint64_t>(blocks); })) return -1;
+  const hipStream_t s = run.s;
   HIPC(ctx, launch_k_mad_peak(d, blocks, iters, s));  // warm-up (clocks, code load)
   HIPC(ctx, hipEventRecord(ctx->ev0, s));
   HIPC(ctx, launch_k_mad_peak(d, blocks, iters, s));
   HIPC(ctx, hipEventRecord(ctx->ev1, s));
-  HIPC(ctx, hipStreamSynchronize(s));
+  if (run.finish()) return -1;
   float ms = 0.f;
   HIPC(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
   double mads = (double)blocks * 256.0 * iters * 16.0 * 8.0;
@@ -2541,16 +2497,48 @@ extern "C" int bls_gpu_fp_mul_test(bls_gpu_ctx* ctx, const uint8_t* a48, const u
   CTX_LOCK(ctx);
   HIPC(ctx, hipSetDevice(ctx->device));
   if (n == 0) return 0;
-  size_t sz = 48ull * n, al = (sz + 255) & ~(size_t)255;
-  if (ensure_dev(ctx, 3 * al)) return -1;
-  uint8_t *da = ctx->dev_ws, *db = da + al, *dout = db + al;
-  hipStream_t s = ctx->stream;
+  const size_t sz = 48ull * n;
+  uint8_t *da = nullptr, *db = nullptr, *dout = nullptr;
+  OneShot run(ctx);
+  if (run.carve([&](Carver& c) { c.buf(da, sz).buf(db, sz).buf(dout, sz); })) return -1;
+  const hipStream_t s = run.s;
   HIPC(ctx, hipMemcpyAsync(da, a48, sz, hipMemcpyHostToDevice, s));
   HIPC(ctx, hipMemcpyAsync(db, b48, sz, hipMemcpyHostToDevice, s));
   HIPC(ctx, launch_k_fp_mul_test(da, db, n, dout, s));
   HIPC(ctx, hipMemcpyAsync(out48, dout, sz, hipMemcpyDeviceToHost, s));
-  HIPC(ctx, hipStreamSynchronize(s));
-  return 0;
+  return run.finish();
+}
+
+// The body of the field, curve and tower op self-tests: n records of iw words in, n of ow
+// words out (zeroed before the launch), and behind them ws_bytes of zeroed workspace (curve
+// ops; none: `launch` gets nullptr).  `launch` names the op's kernel launcher.
+template <class Launch>
+static int op_test(bls_gpu_ctx* ctx, uint32_t iw, uint32_t ow, size_t ws_bytes, const uint32_t* in, uint32_t n,
+                   uint32_t* out, Launch&& launch) {
+  const size_t in_sz = 4ull * iw * n, out_sz = 4ull * ow * n;
+  uint32_t *din = nullptr, *dout = nullptr;
+  uint8_t* dws = nullptr;
+  OneShot run(ctx);
+  if (run.carve([&](Carver& c) { c.buf(din, (size_t)iw * n).buf(dout, (size_t)ow * n).buf(dws, ws_bytes); })) return -1;
+  HIPC(ctx, hipMemcpyAsync(din, in, in_sz, hipMemcpyHostToDevice, run.s));
+  HIPC(ctx, hipMemsetAsync(dout, 0, out_sz, run.s));
+  if (ws_bytes) HIPC(ctx, hipMemsetAsync(dws, 0, ws_bytes, run.s));
+  if (const int rc = launch(din, dout, ws_bytes ? dws : nullptr, run.s)) return rc;
+  HIPC(ctx, hipMemcpyAsync(out, dout, out_sz, hipMemcpyDeviceToHost, run.s));
+  return run.finish();
+}
+
+// The chain rows (PipeBufs::chain) of n records of iw words that begin with RP (x, y, z) and
+// HQ (x.c0, x.c1, y.c0, y.c1): the two at their CH_RP and CH_HQ slots, every other slot zero.
+static std::vector<uint32_t> chain_rows(const uint32_t* in, uint32_t iw, uint32_t n) {
+  std::vector<uint32_t> chain((size_t)CHAIN_WORDS * 12 * n, 0u);
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint32_t* r = in + (size_t)iw * i;
+    uint32_t* row = chain.data() + (size_t)CHAIN_WORDS * 12 * i;
+    memcpy(row + 12 * CH_RP, r, 4 * 36);
+    memcpy(row + 12 * CH_HQ, r + 36, 4 * 48);
+  }
+  return chain;
 }
 
 extern "C" int bls_gpu_field_op_shape(uint32_t op, uint32_t* in_words, uint32_t* out_words) {
@@ -2568,16 +2556,10 @@ extern "C" int bls_gpu_field_op_test(bls_gpu_ctx* ctx, uint32_t op, const uint32
     return -2;
   }
   if (n == 0) return 0;
-  const size_t in_sz = 4ull * iw * n, out_sz = 4ull * ow * n, in_al = (in_sz + 255) & ~(size_t)255;
-  if (ensure_dev(ctx, in_al + out_sz)) return -1;
-  uint32_t *din = (uint32_t*)ctx->dev_ws, *dout = (uint32_t*)(ctx->dev_ws + in_al);
-  hipStream_t s = ctx->stream;
-  HIPC(ctx, hipMemcpyAsync(din, in, in_sz, hipMemcpyHostToDevice, s));
-  HIPC(ctx, hipMemsetAsync(dout, 0, out_sz, s));
-  HIPC(ctx, launch_k_field_op(op, din, n, dout, s));
-  HIPC(ctx, hipMemcpyAsync(out, dout, out_sz, hipMemcpyDeviceToHost, s));
-  HIPC(ctx, hipStreamSynchronize(s));
-  return 0;
+  return op_test(ctx, iw, ow, 0, in, n, out, [&](const uint32_t* din, uint32_t* dout, void*, hipStream_t s) -> int {
+    HIPC(ctx, launch_k_field_op(op, din, n, dout, s));
+    return 0;
+  });
 }
 
 extern "C" int bls_gpu_curve_op_shape(uint32_t op, uint32_t* in_words, uint32_t* out_words) {
@@ -2599,39 +2581,29 @@ static int curve_miller_test(bls_gpu_ctx* ctx, const uint32_t* in, uint32_t n, u
     snprintf(ctx->err, sizeof(ctx->err), "curve op MILLER: %u items, per_lane %u", n, per_lane);
     return -2;
   }
-  std::vector<uint32_t> chain((size_t)CHAIN_WORDS * 12 * n, 0u), live(n, 1u), dom(n);
-  for (uint32_t i = 0; i < n; ++i) {
-    const uint32_t* r = in + (size_t)iw * i;
-    uint32_t* row = chain.data() + (size_t)CHAIN_WORDS * 12 * i;
-    memcpy(row + 12 * CH_RP, r, 4 * 36);
-    memcpy(row + 12 * CH_HQ, r + 36, 4 * 48);
-    dom[i] = r[84];
-  }
-  auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  const size_t chain_sz = al(4 * chain.size()), w_sz = al(4ull * n), f_sz = al(sizeof(Fp12) * (size_t)n),
-               line_sz = al(4 * mlq_line_words(n));
-  if (ensure_dev(ctx, chain_sz + 2 * w_sz + f_sz + line_sz)) return -1;
-  uint8_t* p = ctx->dev_ws;
+  const std::vector<uint32_t> chain = chain_rows(in, iw, n), live(n, 1u);
+  std::vector<uint32_t> dom(n);
+  for (uint32_t i = 0; i < n; ++i) dom[i] = in[(size_t)iw * i + 84];
   PipeBufs b;
   memset(&b, 0, sizeof(b));
   b.n_sets = n;
   b.indiv_vbase = n;
   b.mlf_pl = per_lane;
-  b.chain = (Fp*)p;
-  b.chain_live = (uint32_t*)(p + chain_sz);
-  uint32_t* d_dom = (uint32_t*)(p + chain_sz + w_sz);
-  b.ml_dom = d_dom;
-  b.f = (Fp12*)(p + chain_sz + 2 * w_sz);
-  uint32_t* lines = (uint32_t*)(p + chain_sz + 2 * w_sz + f_sz);
-  hipStream_t s = ctx->stream;
+  uint32_t* lines = nullptr;
+  OneShot run(ctx);
+  if (run.carve([&](Carver& c) {
+        c.buf(b.chain, (size_t)CHAIN_WORDS * n).buf(b.chain_live, n).buf(b.ml_dom, n).buf(b.f, n);
+        c.buf(lines, mlq_line_words(n));
+      }))
+    return -1;
+  const hipStream_t s = run.s;
   HIPC(ctx, hipMemcpyAsync(b.chain, chain.data(), 4 * chain.size(), hipMemcpyHostToDevice, s));
   HIPC(ctx, hipMemcpyAsync(b.chain_live, live.data(), 4ull * n, hipMemcpyHostToDevice, s));
-  HIPC(ctx, hipMemcpyAsync(d_dom, dom.data(), 4ull * n, hipMemcpyHostToDevice, s));
-  HIPC(ctx, hipMemsetAsync(b.f, 0, f_sz, s));
+  HIPC(ctx, hipMemcpyAsync((void*)b.ml_dom, dom.data(), 4ull * n, hipMemcpyHostToDevice, s));
+  HIPC(ctx, hipMemsetAsync(b.f, 0, sizeof(Fp12) * (size_t)n, s));
   HIPC(ctx, launch_k_mlqf(b, 0, n, false, lines, s));
   HIPC(ctx, hipMemcpyAsync(out, b.f, sizeof(Fp12) * (size_t)n, hipMemcpyDeviceToHost, s));
-  HIPC(ctx, hipStreamSynchronize(s));
-  return 0;
+  return run.finish();
 }
 
 // COP_FE: FE(F) == 1 for n Fp12 values, each its own one-request, one-set chunk, through the
@@ -2644,35 +2616,34 @@ static int curve_miller_test(bls_gpu_ctx* ctx, const uint32_t* in, uint32_t n, u
 static int curve_fe_test(bls_gpu_ctx* ctx, const uint32_t* in, uint32_t n, uint32_t* out) {
   std::vector<uint32_t> idx(n + 1);
   for (uint32_t i = 0; i <= n; ++i) idx[i] = i;
-  auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  const size_t f_sz = al(sizeof(Fp12) * (size_t)n), w_sz = al(4ull * (n + 1));
-  if (ensure_dev(ctx, 5 * f_sz + 4 * w_sz)) return -1;
-  uint8_t* p = ctx->dev_ws;
+  std::vector<int32_t> ok(2 * (size_t)n);
   PipeBufs b;
   memset(&b, 0, sizeof(b));
   b.n_chunks = n;
   b.n_reqs = n;
   b.n_sets = n;
-  b.f = (Fp12*)p;
-  Fp12* save = (Fp12*)(p + f_sz);
-  uint32_t* d_idx = (uint32_t*)(p + 5 * f_sz);
+  Fp12* save = nullptr;
+  uint32_t* d_idx = nullptr;
+  int32_t *ok_simt = nullptr, *ok_coop = nullptr;
+  OneShot run(ctx);
+  if (run.carve([&](Carver& c) {
+        c.buf(b.f, n).buf(save, 4ull * n).buf(d_idx, n + 1).buf(b.req_status, n).buf(ok_simt, n).buf(ok_coop, n);
+      }))
+    return -1;
   b.chunk_off = b.chunk_reqs = b.req_off = d_idx;  // chunk c = request c = set c
-  b.req_status = (int32_t*)(p + 5 * f_sz + w_sz);
-  int32_t* ok_simt = (int32_t*)(p + 5 * f_sz + 2 * w_sz);
-  int32_t* ok_coop = (int32_t*)(p + 5 * f_sz + 3 * w_sz);
-  hipStream_t s = ctx->stream;
+  const hipStream_t s = run.s;
   HIPC(ctx, hipMemcpyAsync(b.f, in, sizeof(Fp12) * (size_t)n, hipMemcpyHostToDevice, s));
   HIPC(ctx, hipMemcpyAsync(d_idx, idx.data(), 4ull * (n + 1), hipMemcpyHostToDevice, s));
-  HIPC(ctx, hipMemsetAsync(b.req_status, 0, w_sz, s));
-  HIPC(ctx, hipMemsetAsync(ok_simt, 0xFF, 2 * w_sz, s));  // -1: a kernel that writes nothing shows
+  HIPC(ctx, hipMemsetAsync(b.req_status, 0, 4ull * n, s));
+  HIPC(ctx, hipMemsetAsync(ok_simt, 0xFF, 4ull * n, s));  // -1: a kernel that writes nothing shows
+  HIPC(ctx, hipMemsetAsync(ok_coop, 0xFF, 4ull * n, s));
   b.chunk_ok = ok_simt;
   HIPC(ctx, launch_k_chunk_simt(b, save, s));
   b.chunk_ok = ok_coop;
   HIPC(ctx, launch_k_chunk_coop(b, ctx->coop, s));
-  std::vector<int32_t> ok(2 * (size_t)n);
   HIPC(ctx, hipMemcpyAsync(ok.data(), ok_simt, 4ull * n, hipMemcpyDeviceToHost, s));
   HIPC(ctx, hipMemcpyAsync(ok.data() + n, ok_coop, 4ull * n, hipMemcpyDeviceToHost, s));
-  HIPC(ctx, hipStreamSynchronize(s));
+  if (run.finish()) return -1;
   for (uint32_t i = 0; i < n; ++i) {
     out[2 * i] = (uint32_t)ok[i];
     out[2 * i + 1] = (uint32_t)ok[n + i];
@@ -2694,18 +2665,11 @@ extern "C" int bls_gpu_curve_op_test(bls_gpu_ctx* ctx, uint32_t op, const uint32
   if (n == 0) return 0;
   if ((op & ~COP_D28_FLAG) == COP_MILLER) return curve_miller_test(ctx, in, n, out);
   if ((op & ~COP_D28_FLAG) == COP_FE) return curve_fe_test(ctx, in, n, out);
-  const size_t in_sz = 4ull * iw * n, out_sz = 4ull * ow * n, in_al = (in_sz + 255) & ~(size_t)255,
-               out_al = (out_sz + 255) & ~(size_t)255, ws_sz = curve_op_ws_bytes(op, n);
-  if (ensure_dev(ctx, in_al + out_al + ws_sz)) return -1;
-  uint32_t *din = (uint32_t*)ctx->dev_ws, *dout = (uint32_t*)(ctx->dev_ws + in_al);
-  void* dws = ws_sz ? ctx->dev_ws + in_al + out_al : nullptr;
-  hipStream_t s = ctx->stream;
-  HIPC(ctx, hipMemcpyAsync(din, in, in_sz, hipMemcpyHostToDevice, s));
-  HIPC(ctx, hipMemsetAsync(dout, 0, out_al + ws_sz, s));
-  HIPC(ctx, launch_k_curve_op(op, din, n, dout, dws, s));
-  HIPC(ctx, hipMemcpyAsync(out, dout, out_sz, hipMemcpyDeviceToHost, s));
-  HIPC(ctx, hipStreamSynchronize(s));
-  return 0;
+  return op_test(ctx, iw, ow, curve_op_ws_bytes(op, n), in, n, out,
+                 [&](const uint32_t* din, uint32_t* dout, void* dws, hipStream_t s) -> int {
+                   HIPC(ctx, launch_k_curve_op(op, din, n, dout, dws, s));
+                   return 0;
+                 });
 }
 
 extern "C" int bls_gpu_tower_op_shape(uint32_t op, uint32_t* in_words, uint32_t* out_words) {
@@ -2723,32 +2687,23 @@ static int tower_lines_test(bls_gpu_ctx* ctx, const uint32_t* in, uint32_t n, ui
     return -2;
   }
   const uint32_t iw = 12u * (uint32_t)tower_op_in_fps(TOP_MLQ_LINES), ow = 12u * (uint32_t)tower_op_out_fps(TOP_MLQ_LINES);
-  std::vector<uint32_t> chain((size_t)CHAIN_WORDS * 12 * n, 0u), live(n, 1u);
-  for (uint32_t i = 0; i < n; ++i) {
-    const uint32_t* r = in + (size_t)iw * i;
-    uint32_t* row = chain.data() + (size_t)CHAIN_WORDS * 12 * i;
-    memcpy(row + 12 * CH_RP, r, 4 * 36);
-    memcpy(row + 12 * CH_HQ, r + 36, 4 * 48);
-  }
-  auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  const std::vector<uint32_t> chain = chain_rows(in, iw, n), live(n, 1u);
   const size_t words = mlq_line_words(n), stride = words / ow;
-  const size_t chain_sz = al(4 * chain.size()), w_sz = al(4ull * n), line_sz = al(4 * words);
-  if (ensure_dev(ctx, chain_sz + w_sz + line_sz)) return -1;
-  uint8_t* p = ctx->dev_ws;
+  std::vector<uint32_t> buf(words);
   PipeBufs b;
   memset(&b, 0, sizeof(b));
   b.n_sets = n;
-  b.chain = (Fp*)p;
-  b.chain_live = (uint32_t*)(p + chain_sz);
-  uint32_t* lines = (uint32_t*)(p + chain_sz + w_sz);
-  hipStream_t s = ctx->stream;
+  uint32_t* lines = nullptr;
+  OneShot run(ctx);
+  if (run.carve([&](Carver& c) { c.buf(b.chain, (size_t)CHAIN_WORDS * n).buf(b.chain_live, n).buf(lines, words); }))
+    return -1;
+  const hipStream_t s = run.s;
   HIPC(ctx, hipMemcpyAsync(b.chain, chain.data(), 4 * chain.size(), hipMemcpyHostToDevice, s));
   HIPC(ctx, hipMemcpyAsync(b.chain_live, live.data(), 4ull * n, hipMemcpyHostToDevice, s));
-  HIPC(ctx, hipMemsetAsync(lines, 0, line_sz, s));
+  HIPC(ctx, hipMemsetAsync(lines, 0, 4 * words, s));
   HIPC(ctx, launch_k_mlq_lines(b, n, lines, s));
-  std::vector<uint32_t> buf(words);
   HIPC(ctx, hipMemcpyAsync(buf.data(), lines, 4 * words, hipMemcpyDeviceToHost, s));
-  HIPC(ctx, hipStreamSynchronize(s));
+  if (run.finish()) return -1;
   for (uint32_t k = 0; k < n; ++k)
     for (uint32_t ew = 0; ew < ow; ++ew) out[(size_t)ow * k + ew] = buf[(size_t)ew * stride + k];
   return 0;
@@ -2767,16 +2722,10 @@ extern "C" int bls_gpu_tower_op_test(bls_gpu_ctx* ctx, uint32_t op, const uint32
   }
   if (n == 0) return 0;
   if ((op & ~TOP_D28_FLAG) == TOP_MLQ_LINES) return tower_lines_test(ctx, in, n, out);
-  const size_t in_sz = 4ull * iw * n, out_sz = 4ull * ow * n, in_al = (in_sz + 255) & ~(size_t)255;
-  if (ensure_dev(ctx, in_al + out_sz)) return -1;
-  uint32_t *din = (uint32_t*)ctx->dev_ws, *dout = (uint32_t*)(ctx->dev_ws + in_al);
-  hipStream_t s = ctx->stream;
-  HIPC(ctx, hipMemcpyAsync(din, in, in_sz, hipMemcpyHostToDevice, s));
-  HIPC(ctx, hipMemsetAsync(dout, 0, out_sz, s));
-  HIPC(ctx, launch_k_tower_op(op, din, n, dout, s));
-  HIPC(ctx, hipMemcpyAsync(out, dout, out_sz, hipMemcpyDeviceToHost, s));
-  HIPC(ctx, hipStreamSynchronize(s));
-  return 0;
+  return op_test(ctx, iw, ow, 0, in, n, out, [&](const uint32_t* din, uint32_t* dout, void*, hipStream_t s) -> int {
+    HIPC(ctx, launch_k_tower_op(op, din, n, dout, s));
+    return 0;
+  });
 }
 
 // Dependent Montgomery-product chain: `lanes` lanes (multiple of 64) x `iters` products.
@@ -2786,15 +2735,16 @@ extern "C" int bls_gpu_fpm_bench(bls_gpu_ctx* ctx, uint32_t lanes, uint32_t iter
   CTX_LOCK(ctx);
   HIPC(ctx, hipSetDevice(ctx->device));
   lanes = (lanes + 63) / 64 * 64;
-  if (ensure_dev(ctx, sizeof(Fp) * 2 * lanes)) return -1;
-  Fp* io = (Fp*)ctx->dev_ws;
-  hipStream_t s = ctx->stream;
+  Fp* io = nullptr;
+  OneShot run(ctx);
+  if (run.carve([&](Carver& c) { io = c.take<Fp>(2ull * lanes); })) return -1;
+  const hipStream_t s = run.s;
   HIPC(ctx, hipMemsetAsync(io, 0x11, sizeof(Fp) * 2 * lanes, s));
   HIPC(ctx, launch_k_fpm_chain(io, lanes, 8, s));
   HIPC(ctx, hipEventRecord(ctx->ev0, s));
   HIPC(ctx, launch_k_fpm_chain(io, lanes, iters, s));
   HIPC(ctx, hipEventRecord(ctx->ev1, s));
-  HIPC(ctx, hipStreamSynchronize(s));
+  if (run.finish()) return -1;
   float ms = 0.f;
   HIPC(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
   *ns_per_fpm = ms * 1e6 / iters;
@@ -2810,17 +2760,34 @@ extern "C" int bls_gpu_kernel_probe(bls_gpu_ctx* ctx, const char* name, uint32_t
     snprintf(ctx->err, sizeof(ctx->err), "unknown probe %s", name ? name : "(null)");
     return -2;
   }
-  if (ensure_dev(ctx, per * lanes)) return -1;
-  hipStream_t s = ctx->stream;
-  HIPC(ctx, launch_kernel_probe(name, ctx->dev_ws, lanes, s));  // warm-up
+  uint8_t* d = nullptr;
+  OneShot run(ctx);
+  if (run.carve([&](Carver& c) { d = c.take<uint8_t>(per * lanes); })) return -1;
+  const hipStream_t s = run.s;
+  HIPC(ctx, launch_kernel_probe(name, d, lanes, s));  // warm-up
   HIPC(ctx, hipEventRecord(ctx->ev0, s));
-  for (uint32_t r = 0; r < reps; ++r) HIPC(ctx, launch_kernel_probe(name, ctx->dev_ws, lanes, s));
+  for (uint32_t r = 0; r < reps; ++r) HIPC(ctx, launch_kernel_probe(name, d, lanes, s));
   HIPC(ctx, hipEventRecord(ctx->ev1, s));
-  HIPC(ctx, hipStreamSynchronize(s));
+  if (run.finish()) return -1;
   float t = 0.f;
   HIPC(ctx, hipEventElapsedTime(&t, ctx->ev0, ctx->ev1));
   *ms = t;
   return 0;
+}
+
+// The cooperative program `name` of the loaded table and, with `frame`, its frame size in
+// slots; a null or unknown name: -1 and "no program ...".
+static int coop_lookup(bls_gpu_ctx* ctx, const char* name, CoopProg* pg, uint32_t* frame) {
+  bool found = false;
+  for (size_t k = 0; name && k < ctx->coop_progs->size(); ++k)
+    if ((*ctx->coop_progs)[k].first == name) {
+      *pg = (*ctx->coop_progs)[k].second;
+      if (frame) *frame = (*ctx->coop_frames)[k];
+      found = true;
+    }
+  if (found) return 0;
+  snprintf(ctx->err, sizeof(ctx->err), "no program %s", name ? name : "(null)");
+  return -1;
 }
 
 // Probe: time the cooperative program `name` (blocks x reps runs); us_per_step is the
@@ -2830,25 +2797,17 @@ extern "C" int bls_gpu_coop_probe(bls_gpu_ctx* ctx, const char* name, uint32_t b
   CTX_LOCK(ctx);
   HIPC(ctx, hipSetDevice(ctx->device));
   CoopProg pg{0, 0};
-  bool found = false;
-  for (auto& e : *ctx->coop_progs)
-    if (e.first == name) {
-      pg = e.second;
-      found = true;
-    }
-  if (!found) {
-    snprintf(ctx->err, sizeof(ctx->err), "no program %s", name);
-    return -1;
-  }
-  size_t sink_bytes = (4ull * blocks + 255) & ~(size_t)255;
-  if (ensure_dev(ctx, sink_bytes + 8ull * (2 * pg.n + 1))) return -1;
-  hipStream_t s = ctx->stream;
-  uint64_t* d_stamps = (uint64_t*)(ctx->dev_ws + sink_bytes);
-  HIPC(ctx, launch_k_coop_probe(ctx->coop, pg, blocks, 1, (uint32_t*)ctx->dev_ws, nullptr, s));
+  if (const int rc = coop_lookup(ctx, name, &pg, nullptr)) return rc;
+  uint32_t* sink = nullptr;
+  uint64_t* d_stamps = nullptr;
+  OneShot run(ctx);
+  if (run.carve([&](Carver& c) { c.buf(sink, blocks).buf(d_stamps, 2ull * pg.n + 1); })) return -1;
+  hipStream_t s = run.s;
+  HIPC(ctx, launch_k_coop_probe(ctx->coop, pg, blocks, 1, sink, nullptr, s));
   HIPC(ctx, hipEventRecord(ctx->ev0, s));
-  HIPC(ctx, launch_k_coop_probe(ctx->coop, pg, blocks, reps, (uint32_t*)ctx->dev_ws, nullptr, s));
+  HIPC(ctx, launch_k_coop_probe(ctx->coop, pg, blocks, reps, sink, nullptr, s));
   HIPC(ctx, hipEventRecord(ctx->ev1, s));
-  HIPC(ctx, hipStreamSynchronize(s));
+  if (run.finish()) return -1;
   float ms = 0.f;
   HIPC(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
   *us_per_step = ms * 1e3 / ((double)reps * pg.n);
@@ -2858,12 +2817,13 @@ extern "C" int bls_gpu_coop_probe(bls_gpu_ctx* ctx, const char* name, uint32_t b
     // reach it keep 0)
     const char* me = getenv("BLS_COOP_PROBE_MARK");
     const uint64_t mark = me ? strtoull(me, nullptr, 10) : 0ull;
+    OneShot stamps(ctx);  // (the layout is the timed run's)
     HIPC(ctx, hipMemsetAsync(d_stamps, 0, 8ull * (2 * pg.n + 1), s));
     HIPC(ctx, hipMemcpyAsync(d_stamps, &mark, 8, hipMemcpyHostToDevice, s));
     HIPC(ctx, hipStreamSynchronize(s));
-    HIPC(ctx, launch_k_coop_probe(ctx->coop, pg, 1, 0, (uint32_t*)ctx->dev_ws, d_stamps, s));
+    HIPC(ctx, launch_k_coop_probe(ctx->coop, pg, 1, 0, sink, d_stamps, s));
     HIPC(ctx, hipMemcpyAsync(step_stamps, d_stamps, 8ull * (2 * pg.n + 1), hipMemcpyDeviceToHost, s));
-    HIPC(ctx, hipStreamSynchronize(s));
+    return stamps.finish();
   }
   return 0;
 }
@@ -2878,17 +2838,7 @@ extern "C" int bls_gpu_coop_run_test(bls_gpu_ctx* ctx, const char* name, const u
   HIPC(ctx, hipSetDevice(ctx->device));
   CoopProg pg{0, 0};
   uint32_t frame = 0;
-  bool found = false;
-  for (size_t k = 0; name && k < ctx->coop_progs->size(); ++k)
-    if ((*ctx->coop_progs)[k].first == name) {
-      pg = (*ctx->coop_progs)[k].second;
-      frame = (*ctx->coop_frames)[k];
-      found = true;
-    }
-  if (!found) {
-    snprintf(ctx->err, sizeof(ctx->err), "no program %s", name ? name : "(null)");
-    return -1;
-  }
+  if (const int rc = coop_lookup(ctx, name, &pg, &frame)) return rc;
   if (n_slots != frame || (frame != COOP_FRAME && frame != COOP_FRAME2 && frame != COOP_FRAME3)) {
     snprintf(ctx->err, sizeof(ctx->err), "program %s has a frame of %u slots, not %u", name, frame, n_slots);
     return -2;
@@ -2896,15 +2846,18 @@ extern "C" int bls_gpu_coop_run_test(bls_gpu_ctx* ctx, const char* name, const u
   if (n_frames == 0) return 0;
   const std::string nm(name);
   const bool w2 = nm.size() > 3 && nm.compare(nm.size() - 3, 3, "_w2") == 0;  // two-wavefront programs
-  const size_t fr_sz = sizeof(Fp) * (size_t)frame * n_frames, fr_al = (fr_sz + 255) & ~(size_t)255;
-  if (ensure_dev(ctx, 2 * fr_al + 4ull * n_frames)) return -1;
-  Fp *din = (Fp*)ctx->dev_ws, *dout = (Fp*)(ctx->dev_ws + fr_al);
-  uint32_t* dflags = (uint32_t*)(ctx->dev_ws + 2 * fr_al);
-  hipStream_t s = ctx->stream;
+  const size_t fr_sz = sizeof(Fp) * (size_t)frame * n_frames;
+  Fp *din = nullptr, *dout = nullptr;
+  uint32_t* dflags = nullptr;
+  OneShot run(ctx);
+  if (run.carve([&](Carver& c) {
+        c.buf(din, (size_t)frame * n_frames).buf(dout, (size_t)frame * n_frames).buf(dflags, n_frames);
+      }))
+    return -1;
+  const hipStream_t s = run.s;
   HIPC(ctx, hipMemcpyAsync(din, frames_in, fr_sz, hipMemcpyHostToDevice, s));
   HIPC(ctx, launch_k_coop_run_test(ctx->coop, pg, frame, w2, din, n_frames, dout, dflags, s));
   HIPC(ctx, hipMemcpyAsync(frames_out, dout, fr_sz, hipMemcpyDeviceToHost, s));
   HIPC(ctx, hipMemcpyAsync(flags_out, dflags, 4ull * n_frames, hipMemcpyDeviceToHost, s));
-  HIPC(ctx, hipStreamSynchronize(s));
-  return 0;
+  return run.finish();
 }

@@ -121,3 +121,32 @@ def test_coop_run_rejects_wrong_frame_size(gpu, table):
         gpu.coop_run_test("pset2_prep", np.zeros((1, 256, 12), dtype=np.uint32))  # its frame is 380 slots
     with pytest.raises(NativeError):
         gpu.coop_run_test("no_such_program", np.zeros((1, 256, 12), dtype=np.uint32))
+
+
+def test_coop_probe_finds_its_program_as_the_run_test_does(gpu, table):
+    """bls_gpu_coop_probe looks its program up as bls_gpu_coop_run_test does: a known name is
+    timed (and stamped: 2 * steps + 1 words, none lost behind the blocks' sink), an unknown
+    one is "no program ..." from both."""
+    from lodestar_amd.native import NativeError
+
+    n_steps = table.programs["fin_fmul"][1]
+    us, ms, stamps = gpu.coop_probe("fin_fmul", 3, 1, 2 * n_steps + 1)
+    assert us > 0 and ms > 0 and stamps.shape == (2 * n_steps + 1,)
+    assert all(int(t) != 0 for t in stamps[1:]), "every step of the stamped run starts and ends"
+    for call in (lambda: gpu.coop_probe("no_such_program", 1, 1),
+                 lambda: gpu.coop_run_test("no_such_program", np.zeros((1, 256, 12), dtype=np.uint32))):
+        with pytest.raises(NativeError, match="no program no_such_program"):
+            call()
+
+
+def test_timing_probes_run_and_report(gpu):
+    """The other timing probes have no output to compare: each runs to its end on a small
+    shape and reports a time, and an unknown design probe is refused."""
+    from lodestar_amd.native import NativeError
+
+    ns, rate = gpu.fpm_bench(1024, 64)
+    assert ns > 0 and rate > 0
+    assert gpu.kernel_probe("fpm_d28", 65, 2) > 0
+    assert gpu.mad_peak()[0] > 0
+    with pytest.raises(NativeError, match="unknown probe"):
+        gpu.kernel_probe("no_such_probe", 64, 1)
